@@ -8,8 +8,12 @@
 A "step" is ONE greedy decode step of the whole model (all 48 layers + lm_head + argmax, batch 1) after the
 8x256 prompt has been encoded and prefilled; `value` = steps / max-over-ranks wall time.  Inputs (weights,
 prompt, series tensor) are resident in HBM when the timed region starts.  Extra keys: ttft_ms_p50 (processor +
-H2D + TS encoder + merge + prefill + first token), `roofline` (dominant kernel = the gate_up weight-streaming
-GEMV, timed live with HIP events), `cpu_baseline` (the CPU float32 oracle on this box's host cores, bounded sample).
+H2D + TS encoder + merge + prefill + first token).  A plain run stops there; with --full it also measures
+`roofline` (dominant kernel = the gate_up weight-streaming GEMV, timed live with HIP events), the TS encoder and
+prefill rooflines, the token comparison with the committed full-depth oracle run (`parity`) and `cpu_baseline`
+(the CPU float32 oracle on this box's host cores, bounded sample).
+--dump-outputs DIR writes what the last timed step computed (the generated tokens so far and that step's logits)
+as DIR/<name>.npy, float64 / float32: two builds given the same arguments can be compared output for output.
 Weights are synthetic (counter-hash, bf16-exact) because no checkpoint can reach the box; shapes are the real
 ChatTS-14B ones.  Multi-GPU = tensor parallel (strong scaling), RCCL all-reduce via torch.distributed.
 """
@@ -122,6 +126,38 @@ def pmc_traffic_entry(entry, files_key="code_files"):
 def median(xs):
     s = sorted(xs)
     return s[len(s) // 2]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def vocab_gather(comm, t):
+    """[..., V / world] logits of this rank -> [..., V] on every rank (rank order = vocabulary order); a collective under TP"""
+    import torch
+    if comm.world == 1:
+        return t
+    parts = [torch.empty_like(t) for _ in range(comm.world)]
+    comm.dist.all_gather(parts, t.contiguous(), group=comm.group)
+    return torch.cat(parts, dim=-1)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, integers as float64 (exact), the rest as float32.  Past 64 MB in all, an
+    array keeps a fixed sample of its elements (rng 0, sorted flat indices, stored beside it as <name>_index.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32)
+              for k, v in arrays.items()}
+    total, keep = sum(a.nbytes for a in arrays.values()), 1 << 20
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):          # largest first
+        a = arrays[name]
+        if total > DUMP_LIMIT_BYTES and a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            total -= a.nbytes - keep * (a.itemsize + 8)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step -> {path}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
 
 
 def roofline_gate_up(model, reps=2, m=1):
@@ -456,7 +492,10 @@ def bench_batched(args, model, cfg, comm, world, device):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     toks = Bf["out_tokens_all"][:, :budget].tolist()
-    roof = roofline_gate_up(model, m=B)
+    if args.dump_outputs:
+        logits = vocab_gather(comm, Bf["logits_all"]).cpu().numpy()
+        if comm.rank == 0:
+            dump_outputs(args.dump_outputs, {"tokens": toks, "last_step_logits": logits})
     step_bytes = model.weight_bytes_local()
     names = {"chatts-14b": "ChatTS-14B", "chatts-8b": "ChatTS-8B"}
     label = (f"{names.get(args.model, args.model)} {args.weights} weights, {args.series} series x {args.length} steps, batch {B} continuous "
@@ -482,11 +521,7 @@ def bench_batched(args, model, cfg, comm, world, device):
         "per_sequence_tokens_per_s": args.steps / dt,
         "decode_hbm_gbs_per_gpu": step_bytes / (dt / args.steps) / 1e9,
         "decode_hbm_frac_of_8TBs": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-        "roofline": {"bound": "hbm", "achieved": roof["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": roof["gbs"] / HBM_PEAK_GBS,
-                     "traffic": None, "kernel": roof["kernel"], "avg_us": roof["avg_us"], "bytes_per_launch": roof["bytes_per_launch"],
-                     "launches_timed": roof["launches"]},
     }
-    res["parity_checked"], res["parity"] = parity_check(args, toks)
     res["config"]["rccl_world_size"] = dist.get_world_size() if world > 1 else 1
     # the step also reads every sequence's KV cache (float32 K and V rows of all layers): at 16 sequences x ctx 1.2k that is a
     # third of the step's bytes, so the weight-only rate above understates the HBM stream
@@ -495,6 +530,13 @@ def bench_batched(args, model, cfg, comm, world, device):
     res["decode_kv_bytes_per_step"] = kv_bytes
     res["decode_hbm_gbs_incl_kv"] = (step_bytes + kv_bytes) / (dt / args.steps) / 1e9
     res["decode_hbm_frac_of_8TBs_incl_kv"] = res["decode_hbm_gbs_incl_kv"] / HBM_PEAK_GBS
+    if not args.full:
+        return res
+    roof = roofline_gate_up(model, m=B)
+    res["roofline"] = {"bound": "hbm", "achieved": roof["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": roof["gbs"] / HBM_PEAK_GBS,
+                       "traffic": None, "kernel": roof["kernel"], "avg_us": roof["avg_us"], "bytes_per_launch": roof["bytes_per_launch"],
+                       "launches_timed": roof["launches"]}
+    res["parity_checked"], res["parity"] = parity_check(args, toks)
     try:        # HBM bytes per launch of the dominant kernel from the separate rocprofv3 --pmc FETCH_SIZE pass of THIS workload
         with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
             pmc = json.load(f).get("batched", {}).get(workload_key(args))
@@ -583,7 +625,12 @@ def main():
     ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "int8", "int4"],
                     help="fp8 = BASELINE.json config 5 weight format, int4 = the GPTQ-Int4 checkpoint's (NOT the headline: separate workloads)")
     ap.add_argument("--launch-check", action="store_true", help="only prove the N-rank launch path (no model): rank 0 prints the world it saw")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements after the timed steps: TS encoder time, "
+                    "rooflines, counter traffic, token comparison with the committed oracle run, CPU baseline (--no-cpu-baseline drops it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)          # does not return
@@ -694,7 +741,7 @@ def main():
             if i > 0:                                   # run 0 is the warm-up
                 ttfts.append(dt)
         ttft = median(ttfts)
-        for i in range(args.ttft_runs):                 # the TS encoder alone, host call to results ready (its own loop: a sync inside
+        for i in range(args.ttft_runs if args.full else 0):     # --full: the TS encoder alone, host call to results ready (its own loop: a sync inside
             torch.cuda.synchronize()                    # the TTFT region would stall the launch queue the real generate() keeps full)
             te0 = time.perf_counter()
             model.get_multimodal_embeddings(timeseries=ser, valid_lengths=proc.last_lengths)
@@ -743,6 +790,10 @@ def main():
     toks = model.buf["out_tokens"][:1 + args.warmup + args.steps].tolist()
     tok_s = args.steps / dt
     ms_step = dt / args.steps * 1e3
+    if args.dump_outputs:
+        logits = vocab_gather(comm, model.buf["logits"]).cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"tokens": toks, "last_step_logits": logits})
 
     tp_status = None
     if world > 1:
@@ -750,16 +801,6 @@ def main():
         gathered = [None] * world
         dist.all_gather_object(gathered, int(st_word))
         tp_status = gathered
-    roof = roofline_gate_up(model)
-    traffic, traffic_note, pmc = None, None, None     # HBM bytes per launch from the separate rocprofv3 --pmc pass (TP=1 shape only)
-    try:
-        with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-            pmc = json.load(f)
-        if world == 1 and args.model == "chatts-14b" and args.weights == "bf16":
-            ok, traffic_note = pmc_traffic_entry(pmc)
-            traffic = ok["hbm_bytes_per_launch"] if ok else None
-    except Exception as e:
-        traffic_note = f"profiles/pmc_traffic.json unreadable: {e}"
     step_bytes = model.weight_bytes_local()
     result = {
         "metric": f"generated tokens/sec (greedy, batch 1) + p50 TTFT, {'ChatTS-8B' if args.model == 'chatts-8b' else 'ChatTS-14B'}, "
@@ -783,29 +824,11 @@ def main():
                    "first_tokens": toks[:8],
                    "weight_bytes_decode_stream": step_bytes, "weight_bytes_tiled_prefill_copies": model.tiled_weight_bytes_local(),
                    "weight_bytes_f16q_copies": model.f16q_weight_bytes_local()},
-        "ttft_ms_p50": ttft, "ts_encode_ms_p50": median(enc_ms),
+        "ttft_ms_p50": ttft,
         "decode_hbm_gbs_per_gpu": step_bytes / (dt / args.steps) / 1e9,
         "decode_hbm_frac_of_8TBs": step_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
         "decode_frac_of_bf16_mfma_roofline": (2.0 * step_bytes / 2 / (dt / args.steps)) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-        "roofline": {"bound": "hbm", "achieved": roof["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": roof["gbs"] / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": (pmc or {}).get("source") if traffic else traffic_note, "kernel": roof["kernel"],
-                     "avg_us": roof["avg_us"], "bytes_per_launch": roof["bytes_per_launch"],
-                     "launches_timed": roof["launches"]},
     }
-    result["parity_checked"], result["parity"] = parity_check(args, toks)
-    try:        # north_star: "rocprof HBM GB/s on the TS-encoder" - the encoder's own roofline line, at the workload's shape
-        result["ts_encoder_roofline"] = ts_encoder_roofline(model, ser, lengths)
-        if world == 1 and args.model == "chatts-14b" and (args.series, args.length, args.lengths) == (8, 256, "uniform"):
-            ok, why = pmc_traffic_entry((pmc or {}).get("ts_encoder"))
-            result["ts_encoder_roofline"]["traffic"] = ok["hbm_fetch_bytes_per_call"] if ok else None
-            result["ts_encoder_roofline"]["traffic_source"] = ok["source"] if ok else why
-    except Exception as e:
-        result["ts_encoder_roofline"] = {"error": f"{type(e).__name__}: {e}"}
-    try:        # secondary evidence: MFMA utilisation of the prefill's dominant GEMM (north_star asks for it beside the HBM rate)
-        result["prefill_roofline"] = prefill_mfma_gate_up(model, T)
-    except Exception as e:
-        result["prefill_roofline"] = {"error": f"{type(e).__name__}: {e}"}
     # the prefill END TO END: useful flops of the prompt (2 x decoder parameters streamed per token on this rank; attention and the
     # lm_head of the last row left out) over the measured TTFT (processor + TS encoder + merge + prefill + first token) - the figure
     # that says how far the whole prefill is from the matrix pipe, not its best kernel
@@ -815,12 +838,42 @@ def main():
                              "issued_frac_of_bf16_peak": (2.0 if model.precision == "bf16x2" else 1.0) * useful / (ttft * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
                              "ttft_ms": ttft, "prompt_tokens": T,
                              "note": "issued = useful x 2 in the parity-grade bf16x2 mode (hi and lo pass of every product)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:       # secondary measurements: kernels timed on their own, committed references, the CPU baseline
+        roof = roofline_gate_up(model)
+        traffic, traffic_note, pmc = None, None, None     # HBM bytes per launch from the separate rocprofv3 --pmc pass (TP=1 shape only)
         try:
-            result["cpu_baseline"] = cpu_baseline(model, T, ser=ser)
-        except Exception as e:          # the baseline must never take the GPU number down with it
-            result["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port",
-                                      "sample": f"failed: {type(e).__name__}: {e}"}
+            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                pmc = json.load(f)
+            if world == 1 and args.model == "chatts-14b" and args.weights == "bf16":
+                ok, traffic_note = pmc_traffic_entry(pmc)
+                traffic = ok["hbm_bytes_per_launch"] if ok else None
+        except Exception as e:
+            traffic_note = f"profiles/pmc_traffic.json unreadable: {e}"
+        result["ts_encode_ms_p50"] = median(enc_ms)
+        result["roofline"] = {"bound": "hbm", "achieved": roof["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": roof["gbs"] / HBM_PEAK_GBS, "traffic": traffic,
+                              "traffic_source": (pmc or {}).get("source") if traffic else traffic_note, "kernel": roof["kernel"],
+                              "avg_us": roof["avg_us"], "bytes_per_launch": roof["bytes_per_launch"],
+                              "launches_timed": roof["launches"]}
+        result["parity_checked"], result["parity"] = parity_check(args, toks)
+        try:        # north_star: "rocprof HBM GB/s on the TS-encoder" - the encoder's own roofline line, at the workload's shape
+            result["ts_encoder_roofline"] = ts_encoder_roofline(model, ser, lengths)
+            if world == 1 and args.model == "chatts-14b" and (args.series, args.length, args.lengths) == (8, 256, "uniform"):
+                ok, why = pmc_traffic_entry((pmc or {}).get("ts_encoder"))
+                result["ts_encoder_roofline"]["traffic"] = ok["hbm_fetch_bytes_per_call"] if ok else None
+                result["ts_encoder_roofline"]["traffic_source"] = ok["source"] if ok else why
+        except Exception as e:
+            result["ts_encoder_roofline"] = {"error": f"{type(e).__name__}: {e}"}
+        try:        # secondary evidence: MFMA utilisation of the prefill's dominant GEMM (north_star asks for it beside the HBM rate)
+            result["prefill_roofline"] = prefill_mfma_gate_up(model, T)
+        except Exception as e:
+            result["prefill_roofline"] = {"error": f"{type(e).__name__}: {e}"}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            try:
+                result["cpu_baseline"] = cpu_baseline(model, T, ser=ser)
+            except Exception as e:          # the baseline must never take the GPU number down with it
+                result["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port",
+                                          "sample": f"failed: {type(e).__name__}: {e}"}
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -19,7 +19,7 @@ timeout 300 python tools/tp_exchange_bench.py > "$O/3_exchange_latency.txt" 2>&1
 #    run (parity_checked true), tp_exchange must say "p2p one-shot kernels", status word clean
 for W in 2 4 "$N"; do
   [ "$W" -le "$N" ] || continue
-  timeout 900 python bench.py --gpus "$W" --no-cpu-baseline --steps 32 --warmup 8 > "$O/4_bench_tp$W.json" 2> "$O/4_bench_tp$W.err"
+  timeout 900 python bench.py --gpus "$W" --full --no-cpu-baseline --steps 32 --warmup 8 > "$O/4_bench_tp$W.json" 2> "$O/4_bench_tp$W.err"
   rc=$?
   if [ $rc -eq 0 ]; then python - "$O/4_bench_tp$W.json" <<'PY'
 import json, sys
@@ -37,7 +37,7 @@ done
 #     first-contact test chose the fence is expected to FAIL parity - that is the test's finding, not a bug of this script)
 for W in 2 "$N"; do
   [ "$W" -le "$N" ] || continue
-  CHATTS_TP_BULK_FENCE=1 timeout 900 python bench.py --gpus "$W" --no-cpu-baseline --steps 16 --warmup 4 > "$O/4b_bench_tp${W}_fence.json" 2> "$O/4b_bench_tp${W}_fence.err"
+  CHATTS_TP_BULK_FENCE=1 timeout 900 python bench.py --gpus "$W" --full --no-cpu-baseline --steps 16 --warmup 4 > "$O/4b_bench_tp${W}_fence.json" 2> "$O/4b_bench_tp${W}_fence.err"
   say $? "bench.py --gpus $W with TP_BULK_FENCE=1 (compare ttft_ms / parity_checked with step 4)" "$O/4b_bench_tp${W}_fence.err"
 done
 # 5. the plain-Python call shape of the reference (demo/demo_vllm.py:30): LLM(tensor_parallel_size=2) spawns its follower

@@ -4,7 +4,7 @@
 R="${GRAFT_REPO_ROOT:-.}"; O=$R/gpurun_out; mkdir -p $O; cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0 CHATTS_FORCE_DEVICE=0 CHATTS_DIST_BACKEND=gloo CHATTS_TP_FUSE_BLOCKS=48 CHATTS_TP_BULK_BLOCKS=16 CHATTS_TP_AR_BLOCKS=16
 for W in 2 8; do
-  timeout 900 python bench.py --gpus $W --steps 16 --warmup 4 --no-cpu-baseline --ttft-runs 2 > $O/r4_tp${W}_self_launch_single_device.json 2> $O/r4_tp${W}_self_launch_single_device.err; echo "bench --gpus $W rc=$?"
+  timeout 900 python bench.py --gpus $W --steps 16 --warmup 4 --full --no-cpu-baseline --ttft-runs 2 > $O/r4_tp${W}_self_launch_single_device.json 2> $O/r4_tp${W}_self_launch_single_device.err; echo "bench --gpus $W rc=$?"
   python - <<PY
 import json
 try:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """profiles/pmc_traffic.json from rocprofv3 --pmc FETCH_SIZE passes (the `traffic` leg of bench.py's roofline objects).
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/fs -o p -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --ttft-runs 1
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/fs -o p -- python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --ttft-runs 1
     python tools/pmc_traffic.py headline /tmp/fs/.../p_results.db "<the command above>" profiles/r4_bench_pmc_fetch_size.txt
     rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/fst -o p -- python tools/pmc_traffic.py ts-run
     python tools/pmc_traffic.py ts /tmp/fst/.../p_results.db "<command>" profiles/r4_ts_encoder_pmc_fetch_size.txt
