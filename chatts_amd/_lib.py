@@ -62,8 +62,12 @@ class LinearF16qArgs(C.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("planes_tiled", c_int), ("w_tiled", c_int)]
 
 
+KV_F32 = 0          # ChattsKvCache.dtype / ChattsDecoderBuffers.kv_dtype (CHATTS_KV_F32 / CHATTS_KV_F16)
+KV_F16 = 1
+
+
 class KvCache(C.Structure):
-    _fields_ = [("k", c_void_p), ("v", c_void_p), ("max_ctx", c_int),
+    _fields_ = [("k", c_void_p), ("v", c_void_p), ("max_ctx", c_int), ("dtype", c_int),      # dtype: in the hole after max_ctx
                 ("block_table", c_void_p), ("block_size", c_int), ("table_stride", c_int)]      # paged form: block_table != NULL
 
 
@@ -109,7 +113,8 @@ class DecoderBuffers(C.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("t_max", c_int), ("max_batch", c_int),
                 ("planes_hi", c_void_p), ("planes_lo", c_void_p), ("planes2_hi", c_void_p), ("planes2_lo", c_void_p),
                 ("tp_pair_logit", c_void_p), ("tp_pair_token", c_void_p), ("logits_full", c_void_p),
-                ("kv_block_table", c_void_p), ("kv_block_size", c_int), ("kv_table_stride", c_int), ("kv_pool_blocks", c_int)]
+                ("kv_block_table", c_void_p), ("kv_block_size", c_int), ("kv_table_stride", c_int), ("kv_pool_blocks", c_int),
+                ("kv_dtype", c_int)]      # in the trailing padding: sizeof stays 176
 
 
 # name -> (restype, argtypes); this table IS the list of symbols include/chatts_amd.h declares

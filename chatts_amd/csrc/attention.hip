@@ -13,8 +13,11 @@
 //  * attn_rows_kernel (short prefill chunks, T < 16, and the last-row path): one workgroup per (kv head, query row), 64-key
 //    tiles, online softmax, float32 VALU.  Longer chunks run the flash kernels further down: attn_prefill_bf16x3_kernel (bf16
 //    matrix pipe on hi / lo planes, the default) and attn_prefill_mfma_kernel (exact-f32 MFMA).
-// The KV cache is float32 on purpose: the parity target is the float32 reference path and the cache
-// is ~1% of decode traffic at the benchmark context.
+// The KV cache is float32 by default: the parity target is the float32 reference path and the cache
+// is ~1% of decode traffic at the benchmark context.  An fp16 cache (ChattsKvCache.dtype = CHATTS_KV_F16) is
+// the opt-in speed mode: every kernel that reads or writes the cache is a template on its element type KV (float instantiations =
+// the float32 code), rows are widened to f32 in registers, scores / softmax / P.V stay f32.  attn_prefill_mfma_kernel (option
+// ATTN_BF16X3=0, a debugging aid) is float32 only and refuses an fp16 cache.
 #include <math.h>
 
 #include "common.h"
@@ -28,12 +31,12 @@ namespace chatts {
 // ---------------------------------------------------------------------------------------------------
 // decode: grid (n_kv, n_slots), 64 threads.  Slot s walks tiles s, s + n_slots, ... of 16 keys.
 // ---------------------------------------------------------------------------------------------------
-template <int GMAX, bool EXACT>
+template <int GMAX, bool EXACT, typename KV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void attn_decode_kernel(AttnParams p) {
   __shared__ __attribute__((aligned(16))) float q_s[GMAX * kHeadDim];
   __shared__ __attribute__((aligned(16))) float knew_s[kHeadDim];
   __shared__ __attribute__((aligned(16))) float vnew_s[kHeadDim];
-  attn_decode_wave<GMAX, true, EXACT>(p, blockIdx.x, blockIdx.y, blockIdx.z, threadIdx.x, q_s, knew_s, vnew_s, p.part_o, p.part_ml,
+  attn_decode_wave<GMAX, true, EXACT, KV>(p, blockIdx.x, blockIdx.y, blockIdx.z, threadIdx.x, q_s, knew_s, vnew_s, p.part_o, p.part_ml,
                                       (size_t)blockIdx.z * p.n_q + blockIdx.x * (EXACT ? GMAX : p.n_q / p.n_kv));
 }
 
@@ -50,6 +53,7 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(AttnParams p) 
 //   phase 2  one wave per head: tile max / rescale factor / p = exp(s - m) written back to LDS
 //   phase 3  P.V: thread = (dim, key half), V rows read fully coalesced, 8 loads in flight per thread
 // ---------------------------------------------------------------------------------------------------
+template <typename KV>
 __global__ __launch_bounds__(256) void attn_rows_kernel(AttnParams p) {
   __shared__ __attribute__((aligned(16))) float q_s[kMaxGroup * kHeadDim];
   __shared__ float s_s[kMaxGroup * kTile];
@@ -82,10 +86,10 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(AttnParams p) {
     {
       const int j = j0 + key_l;
       const int jc = j <= pos ? j : pos;
-      const float* kr = p.kc + toff + (size_t)(jc - j0) * kHeadDim + quarter * 4;
+      const KV* kr = kv_ptr<KV>(p.kc) + toff + (size_t)(jc - j0) * kHeadDim + quarter * 4;
       f32x4 kv[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) kv[i] = *reinterpret_cast<const f32x4*>(kr + i * 16);
+      for (int i = 0; i < 8; ++i) kv[i] = kv_widen4(kv_load4(kr + i * 16));
       float dot[kMaxGroup];
 #pragma unroll
       for (int g = 0; g < kMaxGroup; ++g) dot[g] = 0.f;
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(AttnParams p) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int j = jb + b8 + u;
-          vv[u] = p.vc[toff + (size_t)((j <= pos ? j : pos) - j0) * kHeadDim + d_o];
+          vv[u] = (float)kv_ptr<KV>(p.vc)[toff + (size_t)((j <= pos ? j : pos) - j0) * kHeadDim + d_o];
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -417,6 +421,7 @@ __device__ __forceinline__ void split8(const float (&x)[8], abf16x8_t& hi, abf16
   }
 }
 
+template <typename KV>
 __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams p) {
   constexpr int KT = 32, NB = 2, KROW = 272, VROW = 80, PS = 36;
   __shared__ __attribute__((aligned(16))) char k_hi[KT * KROW];
@@ -467,7 +472,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
   // K: thread (key = idx >> 5, 4 dims idx & 31): a wave reads two whole key rows.  V: a lane takes the SAME 4 dims of the key
   // pair (2j, 2j+1), j = lane & 15, so that the transposed store is one 4-byte write per dim - the two keys' bf16 values side
   // by side, 16 lanes = 16 consecutive dwords (the first version wrote 2 bytes per lane: 35 % of all LDS cycles were conflicts).
-  f32x4 kreg[4], vreg[4];
+  typename KvVec4<KV>::T kreg[4], vreg[4];                   // as loaded (fp16: widened in store_tile, after the MFMAs of the tile before)
   const int vj = lane & 15;
   auto load_tile = [&](int kt) {
     const size_t toff = kv_tile_off(kvl, hk, kt * KT);      // first row of the tile (one block-table lookup when paged)
@@ -476,7 +481,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
       const int idx = tid + i * 256;
       const int kkey = idx >> 5, kc4 = idx & 31;
       const int kr = kt * KT + kkey <= kmax ? kkey : kmax - kt * KT;    // clamped row inside the tile; masked by key index below
-      kreg[i] = *reinterpret_cast<const f32x4*>(p.kc + toff + (size_t)kr * kHeadDim + kc4 * 4);
+      kreg[i] = kv_load4(kv_ptr<KV>(p.kc) + toff + (size_t)kr * kHeadDim + kc4 * 4);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -485,7 +490,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
       for (int h = 0; h < 2; ++h) {
         const int vkey = 2 * vj + h;
         const int vr = kt * KT + vkey <= kmax ? vkey : kmax - kt * KT;
-        vreg[2 * i + h] = *reinterpret_cast<const f32x4*>(p.vc + toff + (size_t)vr * kHeadDim + vc4 * 4);
+        vreg[2 * i + h] = kv_load4(kv_ptr<KV>(p.vc) + toff + (size_t)vr * kHeadDim + vc4 * 4);
       }
     }
   };
@@ -494,7 +499,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * 256;
       const int kkey = idx >> 5, kc4 = idx & 31;
-      const float kx[4] = {kreg[i].x, kreg[i].y, kreg[i].z, kreg[i].w};
+      const f32x4 kw = kv_widen4(kreg[i]);
+      const float kx[4] = {kw.x, kw.y, kw.z, kw.w};
       abf16x4_t kh, kl;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -509,8 +515,9 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int vc4 = (tid >> 4) + 16 * i;
-      const float v0[4] = {vreg[2 * i].x, vreg[2 * i].y, vreg[2 * i].z, vreg[2 * i].w};
-      const float v1[4] = {vreg[2 * i + 1].x, vreg[2 * i + 1].y, vreg[2 * i + 1].z, vreg[2 * i + 1].w};
+      const f32x4 w0 = kv_widen4(vreg[2 * i]), w1 = kv_widen4(vreg[2 * i + 1]);
+      const float v0[4] = {w0.x, w0.y, w0.z, w0.w};
+      const float v1[4] = {w1.x, w1.y, w1.z, w1.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         abf16x2_t h, l;
@@ -669,6 +676,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
 // Plane layout, per (kv head, 32-key tile) 32 KB: K_hi [32 keys][128], K_lo, V^T_hi [128 dims][32 slots], V^T_lo; rows past the last
 // key repeat it (finite values behind the causal mask).
 // ---------------------------------------------------------------------------------------------------
+template <typename KV>
 __global__ __launch_bounds__(256) void kv_planes_kernel(AttnParams p, int n_keys, uint16_t* planes) {
   constexpr int KT = 32;
   const int tid = threadIdx.x, kt = blockIdx.x, hk = blockIdx.y;
@@ -681,7 +689,7 @@ __global__ __launch_bounds__(256) void kv_planes_kernel(AttnParams p, int n_keys
     const int idx = tid + i * 256;
     const int key = idx >> 5, c4 = idx & 31;
     const int kr = key <= last ? key : last;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p.kc + toff + (size_t)kr * kHeadDim + c4 * 4);
+    const f32x4 v = kv_widen4(kv_load4(kv_ptr<KV>(p.kc) + toff + (size_t)kr * kHeadDim + c4 * 4));
     const float x[4] = {v.x, v.y, v.z, v.w};
     abf16x4_t h, l;
 #pragma unroll
@@ -703,7 +711,7 @@ __global__ __launch_bounds__(256) void kv_planes_kernel(AttnParams p, int n_keys
     for (int j = 0; j < 4; ++j) {
       const int key = kg * 16 + 4 * g + j;
       const int vr = key <= last ? key : last;
-      const float x = p.vc[toff + (size_t)vr * kHeadDim + d];
+      const float x = (float)kv_ptr<KV>(p.vc)[toff + (size_t)vr * kHeadDim + d];
       const __bf16 hh = (__bf16)x;
       h[j] = hh;
       l[j] = (__bf16)(x - (float)hh);
@@ -986,7 +994,9 @@ static int bind_workspace(AttnParams& p, void* workspace, size_t workspace_bytes
 
 // cache -> kernel parameters; the block-paged form is validated here (every entry point goes through this)
 static int bind_cache(AttnParams& p, const ChattsKvCache* cache) {
-  p.kc = cache->k; p.vc = cache->v; p.max_ctx = cache->max_ctx;
+  CHATTS_REQUIRE(kv_elem_bytes(cache->dtype) != 0, CHATTS_E_BADARG,
+                 "attention: unknown KV cache dtype %d (CHATTS_KV_F32 = 0, CHATTS_KV_F16 = 1)", cache->dtype);
+  p.kc = cache->k; p.vc = cache->v; p.max_ctx = cache->max_ctx; p.kv_f16 = cache->dtype == CHATTS_KV_F16;
   p.table = cache->block_table; p.log_block = 0; p.table_stride = cache->table_stride;
   if (cache->block_table) {
     p.log_block = kv_log_block(cache->block_size);
@@ -1036,6 +1046,8 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
   if (t >= 16 && n_splits <= 4 && (!force_rows || out_hi)) {
     // (64-key tiles were measured too: 155 us vs 148 us at T = 798 - the per-tile work is not what is slow)
     const int bf16x3 = opt_get(OPT_ATTN_BF16X3, 1);      // 0: the float32-MFMA kernel
+    CHATTS_REQUIRE(bf16x3 || !p.kv_f16, CHATTS_E_BADARG,
+                   "attention: the float32-MFMA prefill (option ATTN_BF16X3=0) reads a float32 KV cache only, not an fp16 one");
     // K / V split into bf16 planes once (kv_planes_kernel) when the caller's workspace is free (one key split) and holds them
     const bool planes_on = opt_get(OPT_ATTN_PLANES, 1) != 0;
     const int n_keys = pos0 + t, tiles = (n_keys + 31) / 32;
@@ -1045,7 +1057,8 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
     if (planes) {
       uint16_t* pl = static_cast<uint16_t*>(workspace);
       const int nqt = (t + 63) / 64;
-      hipLaunchKernelGGL(kv_planes_kernel, dim3(tiles, n_kv), dim3(256), 0, as_stream(stream), p, n_keys, pl);
+      if (p.kv_f16) hipLaunchKernelGGL(kv_planes_kernel<_Float16>, dim3(tiles, n_kv), dim3(256), 0, as_stream(stream), p, n_keys, pl);
+      else hipLaunchKernelGGL(kv_planes_kernel<float>, dim3(tiles, n_kv), dim3(256), 0, as_stream(stream), p, n_keys, pl);
       CHATTS_CHECK_LAUNCH("kv_planes");
       p.kv_planes = pl; p.kv_plane_tiles = tiles;
       const bool xcd_on = opt_get(OPT_ATTN_XCD, 1) != 0;
@@ -1054,8 +1067,11 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
       const int G = n_q / n_kv;
       const int grid = p.xcd_share ? 8 * ((G * p.units + p.xcd_share - 1) / p.xcd_share) : n_q * p.units;
       hipLaunchKernelGGL(attn_prefill_planes_kernel, dim3(grid), dim3(256), 0, as_stream(stream), p);
-    } else if (bf16x3) hipLaunchKernelGGL(attn_prefill_bf16x3_kernel, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL(attn_prefill_mfma_kernel<32>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
+    } else if (bf16x3 && p.kv_f16) {
+      hipLaunchKernelGGL(attn_prefill_bf16x3_kernel<_Float16>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
+    } else if (bf16x3) {
+      hipLaunchKernelGGL(attn_prefill_bf16x3_kernel<float>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
+    } else hipLaunchKernelGGL(attn_prefill_mfma_kernel<32>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
     CHATTS_CHECK_LAUNCH("attn_prefill_mfma");
     if (n_splits > 1) {
       hipLaunchKernelGGL(attn_combine_rows_kernel, dim3(t), dim3(256), 0, as_stream(stream), p);
@@ -1063,7 +1079,8 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
     }
     return CHATTS_OK;
   }
-  hipLaunchKernelGGL(attn_rows_kernel, dim3(n_kv, t, n_splits), dim3(256), 0, as_stream(stream), p);
+  if (p.kv_f16) hipLaunchKernelGGL(attn_rows_kernel<_Float16>, dim3(n_kv, t, n_splits), dim3(256), 0, as_stream(stream), p);
+  else hipLaunchKernelGGL(attn_rows_kernel<float>, dim3(n_kv, t, n_splits), dim3(256), 0, as_stream(stream), p);
   CHATTS_CHECK_LAUNCH("attn_rows");
   if (n_splits > 1) {
     hipLaunchKernelGGL(attn_combine_kernel, dim3(n_q, t), dim3(128), 0, as_stream(stream), p);
@@ -1073,6 +1090,19 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
 }
 
 namespace chatts {
+template <typename KV>
+static void launch_decode(const int group, const bool exact, const dim3 grid, const dim3 wave, hipStream_t s, const AttnParams& p) {
+  switch (group) {
+    case 4: if (exact) { hipLaunchKernelGGL((attn_decode_kernel<4, true, KV>), grid, wave, 0, s, p); break; }
+    case 1: case 2: case 3: hipLaunchKernelGGL((attn_decode_kernel<4, false, KV>), grid, wave, 0, s, p); break;
+    case 5: if (exact) hipLaunchKernelGGL((attn_decode_kernel<5, true, KV>), grid, wave, 0, s, p);
+            else hipLaunchKernelGGL((attn_decode_kernel<5, false, KV>), grid, wave, 0, s, p);
+            break;
+    case 6: hipLaunchKernelGGL((attn_decode_kernel<6, false, KV>), grid, wave, 0, s, p); break;
+    default: hipLaunchKernelGGL((attn_decode_kernel<kMaxGroup, false, KV>), grid, wave, 0, s, p); break;
+  }
+}
+
 // chatts_attention_decode_batched with an optional plane output (internal: the decoder's batched step feeds o_proj's
 // weight-streaming kernel directly from the combine)
 int attention_decode_batched_impl(const float* qkv_raw, int batch, int n_q, int n_kv, const float* q_norm_w,
@@ -1096,7 +1126,7 @@ int attention_decode_batched_impl(const float* qkv_raw, int batch, int n_q, int 
   p.t = batch; p.n_q = n_q; p.n_kv = n_kv; p.n_splits = n_splits;
   if (const int rc = bind_cache(p, cache)) return rc;
   p.q_norm_w = q_norm_w; p.k_norm_w = k_norm_w; p.cos_tab = cos_tab; p.sin_tab = sin_tab; p.eps = norm_eps;
-  p.seq_stride = seq_stride; p.out_hi = out_hi; p.out_lo = out_lo; p.kv_round = kv_round_mode();
+  p.seq_stride = seq_stride; p.out_hi = out_hi; p.out_lo = out_lo; p.kv_round = p.kv_f16 ? 0 : kv_round_mode();
   const int rc = bind_workspace(p, workspace, workspace_bytes);
   if (rc) return rc;
   const dim3 grid(n_kv, n_splits, batch);
@@ -1105,15 +1135,8 @@ int attention_decode_batched_impl(const float* qkv_raw, int batch, int n_q, int 
   // built); option ATTN_EXACT=0: the run-time form
   const bool exact = opt_get(OPT_ATTN_EXACT, 1) != 0;
   const dim3 wave(64);
-  switch (n_q / n_kv) {
-    case 4: if (exact) { hipLaunchKernelGGL((attn_decode_kernel<4, true>), grid, wave, 0, as_stream(stream), p); break; }
-    case 1: case 2: case 3: hipLaunchKernelGGL((attn_decode_kernel<4, false>), grid, wave, 0, as_stream(stream), p); break;
-    case 5: if (exact) hipLaunchKernelGGL((attn_decode_kernel<5, true>), grid, wave, 0, as_stream(stream), p);
-            else hipLaunchKernelGGL((attn_decode_kernel<5, false>), grid, wave, 0, as_stream(stream), p);
-            break;
-    case 6: hipLaunchKernelGGL((attn_decode_kernel<6, false>), grid, wave, 0, as_stream(stream), p); break;
-    default: hipLaunchKernelGGL((attn_decode_kernel<kMaxGroup, false>), grid, wave, 0, as_stream(stream), p); break;
-  }
+  if (p.kv_f16) launch_decode<_Float16>(n_q / n_kv, exact, grid, wave, as_stream(stream), p);
+  else launch_decode<float>(n_q / n_kv, exact, grid, wave, as_stream(stream), p);
   CHATTS_CHECK_LAUNCH("attn_decode");
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(n_q, batch), dim3(128), 0, as_stream(stream), p);
   CHATTS_CHECK_LAUNCH("attn_decode_combine");

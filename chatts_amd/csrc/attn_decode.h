@@ -16,7 +16,7 @@ constexpr int kMaxSlots = 64;    // decode: tile slots per kv head (one lane of 
 
 struct AttnParams {
   const float* qkv;   // [T, (n_q + 2 n_kv) * 128]; q already rotated for attn_rows, raw for attn_decode
-  float* kc;          // [n_kv, max_ctx, 128]
+  float* kc;          // [n_kv, max_ctx, 128]: float32, or _Float16 storage when kv_f16 (the kernels are instantiated per type)
   float* vc;
   float* out;         // [T, n_q * 128]
   float* part_ml;     // [T, n_q, n_splits, 2]
@@ -29,7 +29,7 @@ struct AttnParams {
   const float* cos_tab;
   const float* sin_tab;
   float eps;
-  size_t seq_stride;   // batched decode: floats between the caches of consecutive sequences (same layer)
+  size_t seq_stride;   // batched decode: elements between the caches of consecutive sequences (same layer)
   // block-paged cache (ChattsKvCache.block_table != NULL): kc / vc are the layer's pool [n_blocks, n_kv, 2^log_block, 128];
   // sequence b looks its blocks up in table + b * table_stride, seq_stride is not used
   const int32_t* table;
@@ -44,6 +44,7 @@ struct AttnParams {
   // attn_prefill_planes_kernel's 1-D grid: query tiles per head and, when n_kv divides 8, the number of XCDs that share one kv head
   // (8 / n_kv; 0 = no XCD-aware order) - see the kernel
   int units, xcd_share;
+  int kv_f16;          // host side: the cache holds _Float16 (ChattsKvCache.dtype == CHATTS_KV_F16)
 };
 
 // rotate one 128-wide head held as (a = x[lane], b = x[lane+64]) by the wave; optional RMSNorm first
@@ -100,32 +101,98 @@ __device__ __forceinline__ f32x4 kv_stream_load(const float* p) {
   return *reinterpret_cast<const f32x4*>(p);
 #endif
 }
-__device__ __forceinline__ void attn_load_k(const KvLayout& kvl, const float* kcache, const int hk, const int tile, const int pos,
+// fp16 cache (KV = _Float16): the tile arrives as raw halves in the first four registers of each set, widened to f32 by
+// attn_widen_tile just before the tile's arithmetic (not at the load: a conversion there would wait for the prefetched tile).
+//   K: lane (kg, c) loads dims c*8 .. c*8+7 and 64 + c*8 .. of keys kg and 8 + kg, 16 bytes per lane: 8 lanes = one whole 128-byte line;
+//      widened, kv[i] (i < 4) holds dims attn_kdim(i) of key kg and kv[4 + i] the same dims of key 8 + kg;
+//   V: the float32 layout (lane (h, c): dims c*4 .. c*4+3 of key 2 i + h), 8 bytes per lane - 32 lanes = one whole 256-byte row;
+//      keys 2 i + h and 2 (i + 1) + h share raw register i / 2.
+template <typename KV>
+__device__ __forceinline__ int attn_kdim(const int i, const int c) {   // first of the 4 dims a lane holds in kv[i] / kv[4 + i]
+  return sizeof(KV) == 2 ? (i >> 1) * 64 + c * 8 + (i & 1) * 4 : c * 4 + i * 32;
+}
+__device__ __forceinline__ u32x4 kv_stream_load16(const _Float16* p) {
+#if CHATTS_KV_NT
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+#else
+  return *reinterpret_cast<const u32x4*>(p);
+#endif
+}
+__device__ __forceinline__ u32x2 kv_stream_load8(const _Float16* p) {
+#if CHATTS_KV_NT
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+#else
+  return *reinterpret_cast<const u32x2*>(p);
+#endif
+}
+template <typename KV>
+__device__ __forceinline__ void attn_load_k(const KvLayout& kvl, const KV* kcache, const int hk, const int tile, const int pos,
                                             const int lane, f32x4 (&kv)[8]) {
   const int kg = lane >> 3, c = lane & 7;
   const int j0 = tile * kDTile;
   const int ja = j0 + kg <= pos ? j0 + kg : pos;          // clamped addresses (stay inside this tile: pos lies in it); masked below
   const int jb = j0 + 8 + kg <= pos ? j0 + 8 + kg : pos;
   const size_t toff = kv_tile_off(kvl, hk, j0);           // the tile's first row: one table lookup per tile when the cache is paged
-  const float* ka = kcache + toff + (size_t)(ja - j0) * kHeadDim + c * 4;
-  const float* kb = kcache + toff + (size_t)(jb - j0) * kHeadDim + c * 4;
+  if constexpr (sizeof(KV) == 2) {
+    const _Float16* ka = kcache + toff + (size_t)(ja - j0) * kHeadDim + c * 8;
+    const _Float16* kb = kcache + toff + (size_t)(jb - j0) * kHeadDim + c * 8;
+    kv[0] = __builtin_bit_cast(f32x4, kv_stream_load16(ka));
+    kv[1] = __builtin_bit_cast(f32x4, kv_stream_load16(ka + 64));
+    kv[2] = __builtin_bit_cast(f32x4, kv_stream_load16(kb));
+    kv[3] = __builtin_bit_cast(f32x4, kv_stream_load16(kb + 64));
+  } else {
+    const float* ka = kcache + toff + (size_t)(ja - j0) * kHeadDim + c * 4;
+    const float* kb = kcache + toff + (size_t)(jb - j0) * kHeadDim + c * 4;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) kv[i] = kv_stream_load(ka + i * 32);
+    for (int i = 0; i < 4; ++i) kv[i] = kv_stream_load(ka + i * 32);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) kv[4 + i] = kv_stream_load(kb + i * 32);
+    for (int i = 0; i < 4; ++i) kv[4 + i] = kv_stream_load(kb + i * 32);
+  }
 }
-__device__ __forceinline__ void attn_load_v(const KvLayout& kvl, const float* vcache, const int hk, const int tile, const int pos,
+template <typename KV>
+__device__ __forceinline__ void attn_load_v(const KvLayout& kvl, const KV* vcache, const int hk, const int tile, const int pos,
                                             const int lane, f32x4 (&vv)[8]) {
   const int j0 = tile * kDTile, h = lane >> 5, c = lane & 31;
   const size_t toff = kv_tile_off(kvl, hk, j0);
+  if constexpr (sizeof(KV) == 2) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int ju = j0 + 2 * i + h <= pos ? j0 + 2 * i + h : pos;
-    vv[i] = kv_stream_load(vcache + toff + (size_t)(ju - j0) * kHeadDim + c * 4);
+    for (int i = 0; i < 8; i += 2) {
+      const int ju = j0 + 2 * i + h <= pos ? j0 + 2 * i + h : pos;
+      const int jw = j0 + 2 * i + 2 + h <= pos ? j0 + 2 * i + 2 + h : pos;
+      const u32x2 x = kv_stream_load8(vcache + toff + (size_t)(ju - j0) * kHeadDim + c * 4);
+      const u32x2 y = kv_stream_load8(vcache + toff + (size_t)(jw - j0) * kHeadDim + c * 4);
+      vv[i >> 1] = __builtin_bit_cast(f32x4, (u32x4){x.x, x.y, y.x, y.y});
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int ju = j0 + 2 * i + h <= pos ? j0 + 2 * i + h : pos;
+      vv[i] = kv_stream_load(vcache + toff + (size_t)(ju - j0) * kHeadDim + c * 4);
+    }
   }
+}
+// fp16 tile: raw halves (attn_load_k / attn_load_v above) -> the f32 register layout the tile arithmetic reads (exact)
+__device__ __forceinline__ void attn_widen_tile(const f32x4 (&kr)[8], const f32x4 (&vr)[8], f32x4 (&kw)[8], f32x4 (&vw)[8]) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    const f16x8 k = __builtin_bit_cast(f16x8, kr[m]);
+    const f16x8 v = __builtin_bit_cast(f16x8, vr[m]);
+    const int kk = (m >> 1) * 4 + (m & 1) * 2;             // kr[0], kr[1]: key kg -> kw[0..3]; kr[2], kr[3]: key 8 + kg -> kw[4..7]
+    kw[kk] = kv_widen4(__builtin_shufflevector(k, k, 0, 1, 2, 3));
+    kw[kk + 1] = kv_widen4(__builtin_shufflevector(k, k, 4, 5, 6, 7));
+    vw[2 * m] = kv_widen4(__builtin_shufflevector(v, v, 0, 1, 2, 3));
+    vw[2 * m + 1] = kv_widen4(__builtin_shufflevector(v, v, 4, 5, 6, 7));
+  }
+}
+// the value a cache row holds for x: the float32 cache under option KV_ROUND, or the fp16 cache (kv_store's rounding)
+template <typename KV>
+__device__ __forceinline__ float kv_cached_value(const float x, const int kv_round) {
+  if constexpr (sizeof(KV) == 2) return (float)(_Float16)x;
+  else return kv_round_f(x, kv_round);
 }
 
 // -> false: nothing to do for this slot (parked sequence, or the slot lies beyond the context)
+template <typename KV = float>
 __device__ __forceinline__ bool attn_decode_preload(const AttnParams& p, const int hk, const int slot, const int seq, const int lane,
                                                     AttnTileRegs& t) {
   const int pos = p.pos0_dev ? p.pos0_dev[seq] : p.pos0;     // batched decode: one position per sequence
@@ -133,7 +200,7 @@ __device__ __forceinline__ bool attn_decode_preload(const AttnParams& p, const i
   if (pos < 0) return false;                   // parked slot of a batched step: no cache write, no attention (its row is ignored)
   const int ntiles = pos / kDTile + 1;
   if (slot >= ntiles) return false;            // the combine only reads slots < min(ntiles, NS)
-  const float* kcache = p.kc + (p.table ? 0 : (size_t)seq * p.seq_stride);
+  const KV* kcache = kv_ptr<KV>(p.kc) + (p.table ? 0 : (size_t)seq * p.seq_stride);
   const KvLayout kvl{p.table ? p.table + (size_t)seq * p.table_stride : nullptr, p.n_kv, p.max_ctx, p.log_block};
   // K of the first tile only depends on `pos`: issued before the q prologue so that the cache rows, q, cos / sin all travel in
   // the same memory round trip (or, preloaded, in an earlier one); V follows at the head of the second stage - it is not
@@ -149,7 +216,7 @@ __device__ __forceinline__ bool attn_decode_preload(const AttnParams& p, const i
 // other, so the split does not change a single operation of any head.  The wave with g0 == 0 stores the new K / V row.
 // EXACT (round 5): the group IS GMAX heads - `g < gn` is decided by the compiler and the tile body is one straight-line block (the
 // run-time form compiled to ~400 basic blocks, every head's every step behind a scalar branch, no load / FMA interleaving across them).
-template <int GMAX, bool PF, bool EXACT>
+template <int GMAX, bool PF, bool EXACT, typename KV = float>
 __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const int hk, const int slot, const int seq, const int lane,
                                                    AttnTileRegs& t, float* q_s, float* knew_s, float* vnew_s, const int g0, const int gn_rt,
                                                    float* part_o, float* part_ml, const size_t head_base) {
@@ -161,8 +228,8 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
   const int qkv_n = (p.n_q + 2 * p.n_kv) * kHeadDim;
   const float* qkv = p.qkv + (size_t)seq * qkv_n;
   auto qkv_at = [&](const int col) __attribute__((always_inline)) -> float { return qkv[col]; };
-  float* kcache = p.kc + (p.table ? 0 : (size_t)seq * p.seq_stride);
-  float* vcache = p.vc + (p.table ? 0 : (size_t)seq * p.seq_stride);
+  KV* kcache = kv_ptr<KV>(p.kc) + (p.table ? 0 : (size_t)seq * p.seq_stride);
+  KV* vcache = kv_ptr<KV>(p.vc) + (p.table ? 0 : (size_t)seq * p.seq_stride);
   const KvLayout kvl{p.table ? p.table + (size_t)seq * p.table_stride : nullptr, p.n_kv, p.max_ctx, p.log_block};
   const bool owner = ((pos / kDTile) % NS) == slot;
   const float scale = 0.08838834764831845f * 1.4426950408889634f;    // 128^-1/2 * log2(e): the softmax runs on v_exp_f32 (exp2)
@@ -187,18 +254,18 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
       const int ks = (p.n_q + hk) * kHeadDim;
       float a = qkv_at(ks + lane), b = qkv_at(ks + lane + 64);
       norm_rope(a, b, p.k_norm_w, p.eps, c, s, lane);
-      a = kv_round_f(a, p.kv_round); b = kv_round_f(b, p.kv_round);
+      a = kv_cached_value<KV>(a, p.kv_round); b = kv_cached_value<KV>(b, p.kv_round);
       knew_s[lane] = a;
       knew_s[lane + 64] = b;
       const size_t noff = kv_tile_off(kvl, hk, pos);      // row of the new token
-      float* kd = kcache + noff;
-      if (g0 == 0) { kd[lane] = a; kd[lane + 64] = b; }
+      KV* kd = kcache + noff;
+      if (g0 == 0) { kd[lane] = (KV)a; kd[lane + 64] = (KV)b; }
       const int vs = (p.n_q + p.n_kv + hk) * kHeadDim;
-      const float va = kv_round_f(qkv_at(vs + lane), p.kv_round), vb = kv_round_f(qkv_at(vs + lane + 64), p.kv_round);
+      const float va = kv_cached_value<KV>(qkv_at(vs + lane), p.kv_round), vb = kv_cached_value<KV>(qkv_at(vs + lane + 64), p.kv_round);
       vnew_s[lane] = va;
       vnew_s[lane + 64] = vb;
-      float* vd = vcache + noff;
-      if (g0 == 0) { vd[lane] = va; vd[lane + 64] = vb; }
+      KV* vd = vcache + noff;
+      if (g0 == 0) { vd[lane] = (KV)va; vd[lane + 64] = (KV)vb; }
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // single wave: orders the LDS writes above (in-order LDS, no barrier needed)
@@ -215,11 +282,11 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
     if (owner) {                                // the row just produced is not in the cache for this wave yet
       if ((ja <= pos ? ja : pos) == pos) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) kvb[i] = *reinterpret_cast<const f32x4*>(knew_s + kc * 4 + i * 32);
+        for (int i = 0; i < 4; ++i) kvb[i] = *reinterpret_cast<const f32x4*>(knew_s + attn_kdim<KV>(i, kc));
       }
       if ((jb <= pos ? jb : pos) == pos) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) kvb[4 + i] = *reinterpret_cast<const f32x4*>(knew_s + kc * 4 + i * 32);
+        for (int i = 0; i < 4; ++i) kvb[4 + i] = *reinterpret_cast<const f32x4*>(knew_s + attn_kdim<KV>(i, kc));
       }
       const f32x4 vn = *reinterpret_cast<const f32x4*>(vnew_s + vc * 4);
 #pragma unroll
@@ -234,7 +301,7 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
 #pragma unroll
       for (int g = 0; g < GMAX; ++g) {
         if (g < gn) {
-          const f32x4 qv = *reinterpret_cast<const f32x4*>(q_s + g * kHeadDim + kc * 4 + i * 32);      // shared by both keys
+          const f32x4 qv = *reinterpret_cast<const f32x4*>(q_s + g * kHeadDim + attn_kdim<KV>(i, kc));   // shared by both keys
           da[g] = fmaf(kvb[i].x, qv.x, da[g]);
           da[g] = fmaf(kvb[i].y, qv.y, da[g]);
           da[g] = fmaf(kvb[i].z, qv.z, da[g]);
@@ -291,6 +358,16 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
       }
     }
   };
+  // the fp16 cache's tile is widened here, where it is used (the float32 tile goes to tile_body as loaded)
+  auto run_tile = [&](const int tile, f32x4 (&kvr)[8], f32x4 (&vvr)[8]) __attribute__((always_inline)) {
+    if constexpr (sizeof(KV) == 2) {
+      f32x4 kw[8], vw[8];
+      attn_widen_tile(kvr, vvr, kw, vw);
+      tile_body(tile, kw, vw);
+    } else {
+      tile_body(tile, kvr, vvr);
+    }
+  };
   if constexpr (PF) {
     // a slot that walks several tiles (long contexts, batched decode with few slots per sequence) fetches tile t + NS while it
     // works on tile t: two register sets in ping-pong, one memory round trip per PAIR of steps instead of one per tile
@@ -301,12 +378,12 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
       const int n1 = tile + NS;
       const bool h1 = n1 < ntiles;
       if (h1) { attn_load_k(kvl, kcache, hk, n1, pos, lane, kv2); attn_load_v(kvl, vcache, hk, n1, pos, lane, vv2); }
-      tile_body(tile, kv, vv);
+      run_tile(tile, kv, vv);
       if (!h1) break;
       const int n2 = n1 + NS;
       const bool h2 = n2 < ntiles;
       if (h2) { attn_load_k(kvl, kcache, hk, n2, pos, lane, kv); attn_load_v(kvl, vcache, hk, n2, pos, lane, vv); }
-      tile_body(n1, kv2, vv2);
+      run_tile(n1, kv2, vv2);
       if (!h2) break;
       tile = n2;
     }
@@ -316,7 +393,7 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
         attn_load_k(kvl, kcache, hk, tile, pos, lane, kv);
         attn_load_v(kvl, vcache, hk, tile, pos, lane, vv);
       }
-      tile_body(tile, kv, vv);
+      run_tile(tile, kv, vv);
     }
   }
 #pragma unroll
@@ -335,13 +412,13 @@ __device__ __forceinline__ void attn_decode_finish(const AttnParams& p, const in
 
 
 // GMAX >= the group size: the per-head registers are sized by it (a Qwen2-14B group of 5 in registers for 8 costs the third wave per SIMD)
-template <int GMAX = kMaxGroup, bool PF = true, bool EXACT = false>
+template <int GMAX = kMaxGroup, bool PF = true, bool EXACT = false, typename KV = float>
 __device__ __forceinline__ void attn_decode_wave(const AttnParams& p, const int hk, const int slot, const int seq, const int lane,
                                                  float* q_s, float* knew_s, float* vnew_s, float* part_o, float* part_ml,
                                                  const size_t head_base) {
   AttnTileRegs t;
-  if (!attn_decode_preload(p, hk, slot, seq, lane, t)) return;
-  attn_decode_finish<GMAX, PF, EXACT>(p, hk, slot, seq, lane, t, q_s, knew_s, vnew_s, 0, p.n_q / p.n_kv, part_o, part_ml, head_base);
+  if (!attn_decode_preload<KV>(p, hk, slot, seq, lane, t)) return;
+  attn_decode_finish<GMAX, PF, EXACT, KV>(p, hk, slot, seq, lane, t, q_s, knew_s, vnew_s, 0, p.n_q / p.n_kv, part_o, part_ml, head_base);
 }
 
 // out[h] = sum_s e^{m_s - M} o_s / sum_s e^{m_s - M} l_s over the slots that saw keys (<= 64 slots).  One workgroup

@@ -120,7 +120,7 @@ struct KvLayout {
   const int32_t* table;
   int n_kv, max_ctx, log_block;
 };
-// float offset (from the cache / pool base) of row `key` of kv head `hk`
+// element offset (from the cache / pool base, in elements of the cache's type) of row `key` of kv head `hk`
 __device__ __forceinline__ size_t kv_tile_off(const KvLayout& L, int hk, int key) {
   if (L.table == nullptr) return ((size_t)hk * L.max_ctx + key) * kHeadDim;
   const int blk = L.table[key >> L.log_block];
@@ -132,6 +132,26 @@ inline int kv_log_block(int block_size) {
     if (block_size == (1 << l)) return l;
   return -1;
 }
+
+// ---- KV cache element type (ChattsKvCache.dtype) -------------------------------------------------------------------------------
+// The kernels that touch the cache are templated on its element type KV: float (CHATTS_KV_F32, the shipped instantiations) or
+// _Float16 (CHATTS_KV_F16).  The pointers stay `float*` in the parameter blocks; kv_ptr<KV> gives them their type.  Four consecutive
+// elements travel as KvVec4<KV> (f32x4 / 8-byte f16x4) and are widened to f32x4 where they are used: widening is exact.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <typename KV> struct KvVec4;
+template <> struct KvVec4<float> { typedef f32x4 T; };
+template <> struct KvVec4<_Float16> { typedef f16x4 T; };
+template <typename KV>
+__device__ __forceinline__ KV* kv_ptr(float* p) { return reinterpret_cast<KV*>(p); }
+template <typename KV>
+__device__ __forceinline__ const KV* kv_ptr(const float* p) { return reinterpret_cast<const KV*>(p); }
+template <typename KV>
+__device__ __forceinline__ typename KvVec4<KV>::T kv_load4(const KV* p) { return *reinterpret_cast<const typename KvVec4<KV>::T*>(p); }
+__device__ __forceinline__ f32x4 kv_widen4(f32x4 v) { return v; }
+__device__ __forceinline__ f32x4 kv_widen4(f16x4 v) { return __builtin_convertvector(v, f32x4); }
+// host: the cache's dtype -> element size in bytes, 0 for an unknown dtype
+inline size_t kv_elem_bytes(int dtype) { return dtype == CHATTS_KV_F32 ? 4 : dtype == CHATTS_KV_F16 ? 2 : 0; }
 
 // What rope_kv_kernel does to the raw qkv rows of a prefill chunk: per head optional RMSNorm (Qwen3 q_norm / k_norm), rotation by the
 // token's position, q back in place, K / V rows into the cache.  Also carried by the qkv projection's split-K epilogue
@@ -145,13 +165,15 @@ struct RopeFuse {
   const float* sin_tab;
   int pos0;
   const int32_t* pos0_dev;
-  float* kc;
+  float* kc;          // float32, or _Float16 storage when kv_f16 (the kernels are instantiated per type: rope_kv_head<KV>)
   float* vc;
   KvLayout kvl;
-  int kv_round;
+  int kv_round;       // float32 cache only
+  int kv_f16;         // host side: which instantiation the launch picks
 };
 // one 128-wide head of one token, held by a wave as (a, b) = elements (lane, lane + 64); h = head index in [q | k | v] order;
 // `row` = this head's 128 floats of the qkv buffer (q is written back there)
+template <typename KV = float>
 __device__ __forceinline__ void rope_kv_head(float a, float b, int h, int pos, int lane, float* row, const RopeFuse& r);
 
 inline hipStream_t as_stream(chatts_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
@@ -232,6 +254,8 @@ int argmax_batched_scratch(const float* logits, int batch, int64_t logits_stride
 // EXPERIMENT knob (CHATTS_KV_ROUND, default 0 = off): K / V rows are rounded to a narrower format's VALUES as they enter the float32
 // cache - 1 = bf16, 2 = bf16 hi + lo (16 mantissa bits), 3 = fp16 - to measure what such a cache would cost in logits error against
 // the 1e-3 bar before any kernel is rewritten for it.  The cache layout and every kernel stay float32.
+// Mode 3 is the bitwise reference of the fp16 cache (CHATTS_KV_F16): widen(fp16 cache) == the float32 cache written under mode 3.
+// The option applies to the float32 cache only.
 __device__ __forceinline__ float kv_round_f(float v, int mode) {
   if (mode == 1) return (float)(__bf16)v;
   if (mode == 2) { const __bf16 h = (__bf16)v; return (float)h + (float)(__bf16)(v - (float)h); }
@@ -240,12 +264,21 @@ __device__ __forceinline__ float kv_round_f(float v, int mode) {
 }
 inline int kv_round_mode() { return opt_get(OPT_KV_ROUND, 0); }
 
+// The fp16 cache stores (_Float16)x - round to nearest even, the value kv_round_f(x, 3) writes into the float32 cache; |x| > 65504
+// becomes +-inf (a plain conversion, as the reference's fp16 run has it).
+template <typename KV>
+__device__ __forceinline__ void kv_store(KV* dst, float x, int kv_round) {
+  if constexpr (sizeof(KV) == 2) *dst = (KV)x;
+  else *dst = kv_round_f(x, kv_round);
+}
+
+template <typename KV>
 __device__ __forceinline__ void rope_kv_head(float a, float b, int h, int pos, int lane, float* row, const RopeFuse& r) {
 #pragma clang fp contract(off)
   if (h >= r.n_q + r.n_kv) {   // v head: straight copy into the cache
-    float* dst = r.vc + kv_tile_off(r.kvl, h - r.n_q - r.n_kv, pos);
-    dst[lane] = kv_round_f(a, r.kv_round);
-    dst[lane + 64] = kv_round_f(b, r.kv_round);
+    KV* dst = kv_ptr<KV>(r.vc) + kv_tile_off(r.kvl, h - r.n_q - r.n_kv, pos);
+    kv_store(dst + lane, a, r.kv_round);
+    kv_store(dst + lane + 64, b, r.kv_round);
     return;
   }
   const float* nw = h < r.n_q ? r.q_norm_w : r.k_norm_w;
@@ -261,9 +294,9 @@ __device__ __forceinline__ void rope_kv_head(float a, float b, int h, int pos, i
     row[lane] = oa;
     row[lane + 64] = ob;
   } else {
-    float* dst = r.kc + kv_tile_off(r.kvl, h - r.n_q, pos);
-    dst[lane] = kv_round_f(oa, r.kv_round);
-    dst[lane + 64] = kv_round_f(ob, r.kv_round);
+    KV* dst = kv_ptr<KV>(r.kc) + kv_tile_off(r.kvl, h - r.n_q, pos);
+    kv_store(dst + lane, oa, r.kv_round);
+    kv_store(dst + lane + 64, ob, r.kv_round);
   }
 }
 // host: validate the arguments of chatts_rope_kv_write and fill a RopeFuse (elementwise.hip)

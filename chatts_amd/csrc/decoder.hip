@@ -137,6 +137,10 @@ extern "C" ChattsDecoder* chatts_decoder_create(const ChattsDecoderConfig* c, co
   if (c->head_dim != kHeadDim) { set_error("decoder_create: head_dim %d != 128", c->head_dim); return nullptr; }
   if (c->n_q % c->n_kv != 0 || c->n_q / c->n_kv > 8) { set_error("decoder_create: unsupported GQA group"); return nullptr; }
   if (c->hidden % 32 || c->inter % 32) { set_error("decoder_create: hidden/inter must be multiples of 32"); return nullptr; }
+  if (kv_elem_bytes(b->kv_dtype) == 0) {
+    set_error("decoder_create: unknown KV cache dtype %d (CHATTS_KV_F32 = 0, CHATTS_KV_F16 = 1)", b->kv_dtype);
+    return nullptr;
+  }
   if (b->kv_block_table) {
     const int B = b->kv_block_size;
     if (kv_log_block(B) < 0 || c->max_ctx % B != 0 || b->kv_table_stride < c->max_ctx / B || b->kv_pool_blocks < 1) {
@@ -158,25 +162,31 @@ extern "C" ChattsDecoder* chatts_decoder_create(const ChattsDecoderConfig* c, co
 
 extern "C" void chatts_decoder_destroy(ChattsDecoder* d) { delete d; }
 
-static size_t seq_stride(const ChattsDecoder* d) {      // floats between the caches of consecutive sequences
+static size_t seq_stride(const ChattsDecoder* d) {      // elements (of b.kv_dtype) between the caches of consecutive sequences
   return (size_t)d->cfg.n_layers * d->cfg.n_kv * d->cfg.max_ctx * kHeadDim;
+}
+
+// base + `elems` elements of the cache's type (kv_k / kv_v are typed float* in the ABI, the storage may be _Float16)
+static float* kv_at(float* base, size_t elems, int dtype) {
+  return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * kv_elem_bytes(dtype));
 }
 
 static ChattsKvCache layer_cache(const ChattsDecoder* d, int layer, int seq) {
   ChattsKvCache c{};
   c.max_ctx = d->cfg.max_ctx;
+  c.dtype = d->b.kv_dtype;
   if (d->b.kv_block_table) {      // block-paged: the layer's pool + this sequence's row of the block table
     const size_t pool = (size_t)d->b.kv_pool_blocks * d->cfg.n_kv * d->b.kv_block_size * kHeadDim;
-    c.k = d->b.kv_k + pool * layer;
-    c.v = d->b.kv_v + pool * layer;
+    c.k = kv_at(d->b.kv_k, pool * layer, c.dtype);
+    c.v = kv_at(d->b.kv_v, pool * layer, c.dtype);
     c.block_table = d->b.kv_block_table + (size_t)seq * d->b.kv_table_stride;
     c.block_size = d->b.kv_block_size;
     c.table_stride = d->b.kv_table_stride;
     return c;
   }
   const size_t per = (size_t)d->cfg.n_kv * d->cfg.max_ctx * kHeadDim;
-  c.k = d->b.kv_k + seq_stride(d) * seq + per * layer;
-  c.v = d->b.kv_v + seq_stride(d) * seq + per * layer;
+  c.k = kv_at(d->b.kv_k, seq_stride(d) * seq + per * layer, c.dtype);
+  c.v = kv_at(d->b.kv_v, seq_stride(d) * seq + per * layer, c.dtype);
   return c;
 }
 

@@ -51,6 +51,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
 //   out[l]    = x[l]    * cos[l] - x[l+64] * sin[l]
 //   out[l+64] = x[l+64] * cos[l] + x[l]    * sin[l]      (rotate_half / apply_rotary_pos_emb)
 // k (rotated) and v rows go to the cache at position pos; q is rotated in place.
+template <typename KV>
 __global__ __launch_bounds__(256) void rope_kv_kernel(float* __restrict__ qkv, int t, RopeFuse r) {
   const int heads = r.n_q + 2 * r.n_kv;
   const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(float* __restrict__ qkv, i
   const int tok = gw / heads, h = gw - tok * heads;
   const int pos = (r.pos0_dev ? *r.pos0_dev : r.pos0) + tok;
   float* row = qkv + ((size_t)tok * heads + h) * kHeadDim;
-  rope_kv_head(row[lane], row[lane + 64], h, pos, lane, row, r);
+  rope_kv_head<KV>(row[lane], row[lane + 64], h, pos, lane, row, r);
 }
 
 // ---- embedding gather + TS merge -------------------------------------------------------------------
@@ -303,6 +304,8 @@ int rope_fuse_prepare(int t, int n_q, int n_kv, const float* q_norm_w, const flo
                       const float* sin_tab, int pos0, const int32_t* pos0_dev, const ChattsKvCache* cache, RopeFuse* out) {
   CHATTS_REQUIRE(t >= 0 && n_q > 0 && n_kv > 0, CHATTS_E_BADARG, "rope_kv_write: bad sizes");
   CHATTS_REQUIRE(cos_tab && sin_tab && cache && cache->k && cache->v, CHATTS_E_BADARG, "rope_kv_write: null pointer");
+  CHATTS_REQUIRE(kv_elem_bytes(cache->dtype) != 0, CHATTS_E_BADARG,
+                 "rope_kv_write: unknown KV cache dtype %d (CHATTS_KV_F32 = 0, CHATTS_KV_F16 = 1)", cache->dtype);
   CHATTS_REQUIRE((q_norm_w == nullptr) == (k_norm_w == nullptr), CHATTS_E_BADARG,
                  "rope_kv_write: q_norm and k_norm must both be set or both be null");
   if (!pos0_dev)
@@ -315,7 +318,8 @@ int rope_fuse_prepare(int t, int n_q, int n_kv, const float* q_norm_w, const flo
                    "rope_kv_write: block_size %d must be a power of two in 64..32768 that divides max_ctx %d", cache->block_size,
                    cache->max_ctx);
   }
-  *out = RopeFuse{n_q, n_kv, q_norm_w, k_norm_w, norm_eps, cos_tab, sin_tab, pos0, pos0_dev, cache->k, cache->v, kvl, kv_round_mode()};
+  *out = RopeFuse{n_q, n_kv, q_norm_w, k_norm_w, norm_eps, cos_tab, sin_tab, pos0, pos0_dev, cache->k, cache->v, kvl,
+                  cache->dtype == CHATTS_KV_F32 ? kv_round_mode() : 0, cache->dtype == CHATTS_KV_F16};
   return CHATTS_OK;
 }
 }  // namespace chatts
@@ -330,7 +334,8 @@ extern "C" int chatts_rope_kv_write(float* qkv, int t, int n_q, int n_kv, const 
   RopeFuse r;
   if (const int rc = rope_fuse_prepare(t, n_q, n_kv, q_norm_w, k_norm_w, norm_eps, cos_tab, sin_tab, pos0, pos0_dev, cache, &r)) return rc;
   const int waves = t * (n_q + 2 * n_kv);
-  hipLaunchKernelGGL(rope_kv_kernel, dim3((waves + 3) / 4), dim3(256), 0, as_stream(stream), qkv, t, r);
+  if (r.kv_f16) hipLaunchKernelGGL(rope_kv_kernel<_Float16>, dim3((waves + 3) / 4), dim3(256), 0, as_stream(stream), qkv, t, r);
+  else hipLaunchKernelGGL(rope_kv_kernel<float>, dim3((waves + 3) / 4), dim3(256), 0, as_stream(stream), qkv, t, r);
   CHATTS_CHECK_LAUNCH("rope_kv_write");
   return CHATTS_OK;
 }

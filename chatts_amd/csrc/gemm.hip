@@ -781,6 +781,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_norm_q_kernel(const float
 // The qkv projection's split-K epilogue that also does rope_kv_kernel's work (prefill): one wave per (token, head) sums the head's
 // 128 columns over the slabs in split order, adds the bias - splitk_epilogue_kernel's arithmetic - and hands the two values per lane
 // to rope_kv_head: q rotated into c, K / V rows into the cache.  One pass over the [T, 7168] rows less per layer.
+template <typename KV>
 __global__ __launch_bounds__(256) void splitk_epilogue_rope_kernel(const float* __restrict__ ws, int sk, int m, int n,
                                                                   const float* __restrict__ bias, float* __restrict__ c, int ldc,
                                                                   RopeFuse r) {
@@ -802,7 +803,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_rope_kernel(const float* 
   for (; s < sk; ++s) { a += ws[s * plane + at]; b += ws[s * plane + at + 64]; }
   if (bias) { a += bias[h * kHeadDim + lane]; b += bias[h * kHeadDim + lane + 64]; }
   const int pos = (r.pos0_dev ? *r.pos0_dev : r.pos0) + tok;
-  rope_kv_head(a, b, h, pos, lane, c + (size_t)tok * ldc + h * kHeadDim, r);
+  rope_kv_head<KV>(a, b, h, pos, lane, c + (size_t)tok * ldc + h * kHeadDim, r);
 }
 
 static void pick_geometry(int m, int n, int k, int& bm, int& sk, int slots_per_cu = 3, int bn = 128) {
@@ -1059,8 +1060,12 @@ int launch_gemm(const ChattsLinearArgs* a_in, hipStream_t s, const RopeFuse* rop
   if (sk > 1 && rope && rope_done && !post_norm && a->epilogue == CHATTS_EPI_NONE && !a->c_hi && !a->w8 &&
       a->n == (rope->n_q + 2 * rope->n_kv) * kHeadDim) {
     const int waves = a->m * (rope->n_q + 2 * rope->n_kv);
-    hipLaunchKernelGGL(splitk_epilogue_rope_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, reinterpret_cast<const float*>(a->workspace),
-                       sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
+    if (rope->kv_f16)
+      hipLaunchKernelGGL(splitk_epilogue_rope_kernel<_Float16>, dim3((waves + 3) / 4), dim3(256), 0, s,
+                         reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
+    else
+      hipLaunchKernelGGL(splitk_epilogue_rope_kernel<float>, dim3((waves + 3) / 4), dim3(256), 0, s,
+                         reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
     CHATTS_CHECK_LAUNCH("splitk_epilogue_rope");
     *rope_done = true;
     return CHATTS_OK;

@@ -54,7 +54,7 @@ def _build_llm(model, kw):
 class LLM:
     def __init__(self, model, tensor_parallel_size=1, max_model_len=6000, limit_mm_per_prompt=None,
                  trust_remote_code=True, gpu_memory_utilization=None, seed=0, tokenizer=None, comm=None,
-                 max_num_seqs=1, block_size=None, num_gpu_blocks_override=None, **kw):
+                 max_num_seqs=1, block_size=None, num_gpu_blocks_override=None, kv_cache_dtype=None, **kw):
         from .config import PRESETS, ChatTSConfig, preset
         from .modeling import ChatTSForCausalLM
         from .processing import ChatTSProcessor
@@ -69,7 +69,8 @@ class LLM:
                 args = dict(tensor_parallel_size=tensor_parallel_size, max_model_len=max_model_len,
                             limit_mm_per_prompt=limit_mm_per_prompt, trust_remote_code=trust_remote_code,
                             gpu_memory_utilization=gpu_memory_utilization, seed=seed, tokenizer=tokenizer,
-                            max_num_seqs=max_num_seqs, block_size=block_size, num_gpu_blocks_override=num_gpu_blocks_override, **kw)
+                            max_num_seqs=max_num_seqs, block_size=block_size, num_gpu_blocks_override=num_gpu_blocks_override,
+                            kv_cache_dtype=kv_cache_dtype, **kw)
                 group, inner = TpGroup.launch(tensor_parallel_size, _build_llm, (model, args))
                 self.__dict__.update(inner.__dict__)
                 self._tp_group = group
@@ -83,8 +84,10 @@ class LLM:
         # max_num_seqs (vLLM's name): cache slots decoded together (continuous batching); 1 = one request at a time
         # block_size / num_gpu_blocks_override (vLLM's names): block-paged KV cache; fewer blocks than
         # max_num_seqs x max_model_len / block_size oversubscribes the slots (requests then wait for blocks at admission)
+        # kv_cache_dtype (vLLM's name): None / "auto" = the float32 KV cache, "fp16" = the half-size speed mode (ChatTSForCausalLM)
         mk = dict(comm=comm, max_ctx=max_model_len, max_prefill_tokens=min(2048, max_model_len),
-                  max_batch=max(1, int(max_num_seqs)), kv_block_size=block_size, kv_pool_blocks=num_gpu_blocks_override)
+                  max_batch=max(1, int(max_num_seqs)), kv_block_size=block_size, kv_pool_blocks=num_gpu_blocks_override,
+                  kv_cache_dtype=kv_cache_dtype)
         if isinstance(model, ChatTSConfig):
             self.model = ChatTSForCausalLM.from_synthetic(model, seed=seed, **mk)
         elif isinstance(model, str) and model in PRESETS:

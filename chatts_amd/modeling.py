@@ -94,12 +94,25 @@ def rope_tables(cfg, max_pos, device):
     return fr.cos().contiguous().to(device), fr.sin().contiguous().to(device)
 
 
+KV_CACHE_DTYPES = {None: "float32", "auto": "float32", "float32": "float32", "fp16": "float16", "float16": "float16", "half": "float16"}
+
+
+def kv_cache_dtype_name(kv_cache_dtype):
+    """kv_cache_dtype (vLLM's name) -> "float32" or "float16"; ValueError for anything else (fp8 included)."""
+    try:
+        return KV_CACHE_DTYPES[kv_cache_dtype]
+    except (KeyError, TypeError):
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: accepted are None / 'auto' / 'float32' (the float32 cache) and "
+                         "'fp16' / 'float16' / 'half'") from None
+
+
 class ChatTSForCausalLM:
     packed_modules_mapping = packed_modules_mapping
 
     def __init__(self, config, device="cuda", comm=None, max_ctx=2048, max_prefill_tokens=2048, use_graph=True,
                  max_batch=1, weight_format="bf16", use_p2p=True, enable_prefix_caching=True, kv_block_size=None,
-                 kv_pool_blocks=None, precision=None, prefill_tiled_weights=None):
+                 kv_pool_blocks=None, precision=None, prefill_tiled_weights=None, kv_cache_dtype=None):
+        kv_name = kv_cache_dtype_name(kv_cache_dtype)       # (checked before anything touches the device)
         if not torch.cuda.is_available():
             raise RuntimeError("chatts_amd needs a ROCm GPU: there is no CPU fallback for the model")
         self.lib = _lib.load()
@@ -115,6 +128,12 @@ class ChatTSForCausalLM:
         # on the f16 MFMA and an e4m3 residual x e4m3 weights on the CDNA4 block-scaled fp8 MFMA (1.5 instead of 2 pass-equivalents per
         # product; logits ~1.3e-4 of the float32 oracle against ~5e-5).  Measured SLOWER than the default (the kernel is paced by its
         # operand feed, which the split does not shrink) and costs 3 more bytes per weight: opt-in, never the default.  Per model.
+        # kv_cache_dtype: None / "auto" / "float32" = the float32 KV cache (parity grade, the default).  "fp16" / "float16" / "half" =
+        # SPEED mode: K / V rows stored as IEEE fp16 ((_Float16)x, round to nearest even; |x| > 65504 becomes inf, as in the reference's
+        # fp16 run), half the cache bytes - twice the slots, context or paged pool in the same memory, half the decode attention's
+        # stream (config 5: 5.62 -> 5.26 ms per step).  Logits 1.86e-3 of the float32 oracle at full depth, tokens equal (the float32
+        # cache under option KV_ROUND=3 computes the same values; profiles/kv_fp16_ab.txt): NOT parity grade against the 1e-3 bar.
+        # Scores, softmax and P.V stay float32.  Per model.
         if precision not in (None, "bf16x2", "bf16", "fp8", "f16q"):
             raise ValueError("precision must be None / 'bf16x2' or 'f16q' (parity grade), 'bf16' or 'fp8' (speed modes)")
         if precision == "fp8" and weight_format != "fp8":
@@ -122,6 +141,7 @@ class ChatTSForCausalLM:
         if precision is not None:
             _lib.set_option("GEMM_PRECISION", 1 if precision == "bf16" else None)
         self.precision = precision or "bf16x2"
+        self.kv_cache_dtype = getattr(torch, kv_name)
         self.device = torch.device(device)
         self.comm = comm or LocalComm()
         self.plan = ShardPlan(config, self.comm.rank, self.comm.world)
@@ -378,8 +398,8 @@ class ChatTSForCausalLM:
         else:
             kv_shape = (MB, L, plan.nkv, self.max_ctx, d)                     # slot-major: one contiguous cache per sequence
         B = {
-            "kv_k": torch.zeros(kv_shape, **f32),
-            "kv_v": torch.zeros(kv_shape, **f32),
+            "kv_k": torch.zeros(kv_shape, dtype=self.kv_cache_dtype, device=dev),
+            "kv_v": torch.zeros(kv_shape, dtype=self.kv_cache_dtype, device=dev),
             "kv_table": torch.zeros((MB, self.max_ctx // self.kv_block_size), dtype=torch.int32, device=dev) if self.kv_block_size else None,
             "x": torch.zeros((self.t_max, H), **f32), "xn": torch.zeros((self.t_max, H), **f32),
             "qkv": torch.zeros((self.t_max, qkv_n), **f32), "attn": torch.zeros((self.t_max, plan.nq * d), **f32),
@@ -484,7 +504,8 @@ class ChatTSForCausalLM:
                                  tp_pair_token=_lib.ptr(B["tp_pair_token"]), logits_full=_lib.ptr(B["logits_full"]),
                                  kv_block_table=_lib.ptr(B["kv_table"]), kv_block_size=self.kv_block_size,
                                  kv_table_stride=(self.max_ctx // self.kv_block_size) if self.kv_block_size else 0,
-                                 kv_pool_blocks=self._kv.n_blocks if self._kv is not None else 0)
+                                 kv_pool_blocks=self._kv.n_blocks if self._kv is not None else 0,
+                                 kv_dtype=_lib.KV_F16 if self.kv_cache_dtype == torch.float16 else _lib.KV_F32)
         h = lib.chatts_decoder_create(C.byref(dc), C.byref(dw), C.byref(db))
         if not h:
             raise _lib.ChattsError(-1, lib.chatts_last_error().decode())
@@ -554,6 +575,10 @@ class ChatTSForCausalLM:
         T = self._tensors
         head = (T["lm_head8"].numel() + T["lm_head8_scale"].numel() * 4) if "lm_head8" in T else T["lm_head"].numel() * 2
         return n + head + T["final_norm"].numel() * 4
+
+    def kv_cache_bytes_local(self):
+        """Bytes of this rank's K and V caches (every slot, or the paged pool): halved by kv_cache_dtype="fp16"."""
+        return sum(self.buf[k].numel() * self.buf[k].element_size() for k in ("kv_k", "kv_v"))
 
     def tiled_weight_bytes_local(self):
         """Bytes of the prefill kernel's tiled weight copies on this rank (resident beside the tensors weight_bytes_local() counts)."""

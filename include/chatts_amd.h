@@ -7,7 +7,8 @@
  * Device pointers are owned by the caller (PyTorch-ROCm is used purely as the allocator).
  *
  * Each function cites the reference interface (file:line under NetManAIOps/ChatTS) it replaces.
- * Number formats: activations / residual stream / KV cache / logits are float32; weights are
+ * Number formats: activations / residual stream / KV cache / logits are float32 (the KV cache may be fp16 on request:
+ * ChattsKvCache.dtype); weights are
  * bfloat16 (uint16_t bit patterns) streamed from HBM; every weight x activation product is formed
  * either exactly on the f32 VALU (decode, M == 1) or by two bf16 MFMA passes over a hi/lo split of the
  * f32 activation ("bf16x2": batched decode M = 2..16, prefill, TS MLP) - see DESIGN.md section 3 for why (1e-3 logit tolerance).
@@ -353,10 +354,15 @@ int chatts_rmsnorm(const float* x, const float* w, float* y, int t, int hidden, 
 int chatts_rmsnorm_planes(const float* x, const float* w, chatts_bf16* hi, chatts_bf16* lo, int ld_planes, int t, int hidden,
                           float eps, chatts_stream_t stream);
 
+#define CHATTS_KV_F32 0          /* ChattsKvCache.dtype / ChattsDecoderBuffers.kv_dtype: float32 rows (the default, zero) */
+#define CHATTS_KV_F16 1          /* IEEE binary16 rows (_Float16), written as (_Float16)x: round to nearest even, |x| > 65504 -> +-inf */
+
 typedef struct ChattsKvCache {
-  float* k;                /* [n_kv, max_ctx, 128] float32 of ONE layer of ONE sequence */
+  float* k;                /* [n_kv, max_ctx, 128] of ONE layer of ONE sequence: float32, or _Float16 storage when dtype == CHATTS_KV_F16 */
   float* v;
   int max_ctx;             /* positions the sequence may reach */
+  int dtype;               /* CHATTS_KV_F32 (0) or CHATTS_KV_F16; any other value is refused (CHATTS_E_BADARG) before anything is
+                            * enqueued.  Every offset and stride of the cache counts elements of this type. */
   /* Block-paged form (the vLLM engine's KV layout), selected by block_table != NULL: k / v then
    * point at ONE layer's block POOL [n_blocks, n_kv, block_size, 128] shared by all sequences, and position j of this
    * sequence lives in block block_table[j / block_size], row j % block_size.  block_size: a power of two, 64..32768;
@@ -366,6 +372,11 @@ typedef struct ChattsKvCache {
   int block_size;
   int table_stride;
 } ChattsKvCache;
+#ifdef __cplusplus
+static_assert(sizeof(ChattsKvCache) == 40 && offsetof(ChattsKvCache, max_ctx) == 16 && offsetof(ChattsKvCache, dtype) == 20 &&
+                  offsetof(ChattsKvCache, block_table) == 24,
+              "ChattsKvCache layout (dtype lives in the hole after max_ctx)");
+#endif
 
 /* In-place on qkv [T, (n_q+2*n_kv)*128] (after bias): optional per-head RMSNorm of q and k (Qwen3
  * q_norm/k_norm, NULL for Qwen2), NeoX rotate-half RoPE at positions pos0..pos0+T-1 (pos0 read from
@@ -401,7 +412,7 @@ int chatts_attention_decode_fused(const float* qkv_raw, int n_q, int n_kv, const
                                   size_t workspace_bytes, chatts_stream_t stream);
 
 /* Batched form of the above: `batch` sequences, one decode token each; row b of qkv_raw / out and pos_dev[b] belong
- * to sequence b, whose cache is `cache` advanced by b * seq_stride floats (same layer). */
+ * to sequence b, whose cache is `cache` advanced by b * seq_stride elements of the cache's dtype (same layer). */
 int chatts_attention_decode_batched(const float* qkv_raw, int batch, int n_q, int n_kv, const float* q_norm_w,
                                     const float* k_norm_w, float norm_eps, const float* cos_tab,
                                     const float* sin_tab, int pos, const int32_t* pos_dev,
@@ -616,7 +627,7 @@ typedef struct ChattsDecoderWeights {
 } ChattsDecoderWeights;
 
 typedef struct ChattsDecoderBuffers {
-  float* kv_k;        /* [n_layers, n_kv, max_ctx, 128] per sequence (or block pools, see kv_block_table below) */
+  float* kv_k;        /* [n_layers, n_kv, max_ctx, 128] per sequence (or block pools, see kv_block_table below); element type: kv_dtype */
   float* kv_v;
   float* x;           /* [T_max, H] residual stream */
   float* xn;          /* [T_max, H] normed scratch (prefill) */
@@ -649,7 +660,13 @@ typedef struct ChattsDecoderBuffers {
   int kv_block_size;
   int kv_table_stride;
   int kv_pool_blocks;
+  int kv_dtype;       /* CHATTS_KV_F32 (0) or CHATTS_KV_F16: element type of kv_k / kv_v (same shapes); fixed for the decoder's life */
 } ChattsDecoderBuffers;
+#ifdef __cplusplus
+static_assert(sizeof(ChattsDecoderBuffers) == 176 && offsetof(ChattsDecoderBuffers, kv_pool_blocks) == 168 &&
+                  offsetof(ChattsDecoderBuffers, kv_dtype) == 172,
+              "ChattsDecoderBuffers layout (kv_dtype lives in the trailing padding)");
+#endif
 
 typedef struct ChattsDecoder ChattsDecoder;  /* opaque; host memory only */
 ChattsDecoder* chatts_decoder_create(const ChattsDecoderConfig*, const ChattsDecoderWeights*,

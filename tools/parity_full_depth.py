@@ -36,6 +36,7 @@ def main():
     ap.add_argument("--new", type=int, default=9, help="first token + decode steps compared")
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--precision", default=None, choices=[None, "bf16x2", "f16q"], help="f16q: the opt-in parity-grade prefill on the f16 + fp8 matrix pipes")
+    ap.add_argument("--kv-cache-dtype", default=None, choices=[None, "auto", "fp16"], help="fp16: the half-size KV cache (speed mode)")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--out", default="gpurun_out/r3_parity_full.json")
     args = ap.parse_args()
@@ -67,7 +68,7 @@ def main():
     T = len(ids) - 2 * len(lengths) + sum((L + 15) // 16 for L in lengths)
     max_ctx = max(2048, -(-(T + args.new + 16) // 256) * 256)
     model = ChatTSForCausalLM.from_synthetic(cfg, seed=0, max_ctx=max_ctx, max_prefill_tokens=1024, weight_format=args.weights,
-                                             max_batch=B, precision=args.precision)
+                                             max_batch=B, precision=args.precision, kv_cache_dtype=args.kv_cache_dtype)
     model.use_graph = True
 
     # ---- HIP path, driven like bench.py ---------------------------------------------------------------------
@@ -134,7 +135,7 @@ def main():
                                                 weights=args.weights, batch=B))
     res = {
         "what": "full-depth parity of a bench.py workload: HIP path vs CPU float32 oracle (layer-streamed)",
-        "workload_key": key, "precision": args.precision or "bf16x2", "model": args.model, "layers": cfg.num_hidden_layers, "series": args.series,
+        "workload_key": key, "precision": args.precision or "bf16x2", "kv_cache_dtype": args.kv_cache_dtype or "auto", "model": args.model, "layers": cfg.num_hidden_layers, "series": args.series,
         "length": None if args.lengths == "mixed" else args.length, "lengths": lengths, "batch": B, "weights": args.weights,
         "prompt_tokens": per_slot[str(slots[0])]["prompt_tokens"], "seed": 0, "tolerance": 1e-3,
         "max_step_logits_rel_err": worst_rel, "max_abs_err_over_max_logit": worst_abs,
