@@ -29,6 +29,7 @@ class TsWeights(C.Structure):
                 ("b", c_void_p * 8)]
 
 
+LOGPROBS_MAX_K = 64       # CHATTS_LOGPROBS_MAX_K of include/chatts_amd.h
 ABI_VERSION = 9            # CHATTS_ABI_VERSION of include/chatts_amd.h this binding was written against (checked by load())
 W8_FP8, W8_INT8 = 0, 1     # ChattsLinearArgs.w8_format
 
@@ -172,6 +173,11 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "chatts_sample_batched": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, C.POINTER(SamplingArgs), c_void_p, c_void_p,
                                       c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+    "chatts_logprobs_workspace": (c_size_t, [c_int, c_int]),
+    "chatts_logprobs_batched": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chatts_decoder_logprobs": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     "chatts_embed_token_batched": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "chatts_decoder_select_sequence": (c_int, [c_void_p, c_int]),
     "chatts_decoder_set_sampling": (c_int, [c_void_p, C.POINTER(SamplingArgs)]),

@@ -287,6 +287,33 @@ extern "C" int chatts_decoder_select_tokens(ChattsDecoder* d, const float* logit
                                pos_dev, pos_limit, stream);
 }
 
+// Logprobs of the tokens chatts_decoder_select_tokens just chose (see the header).  Under tensor parallelism every rank gathers the
+// full-vocabulary logits into buffers.logits_full (the sampled selection's chatts_allgather) and runs the same kernel on them: the
+// same launches on the same bytes, so every rank writes the same bits.
+extern "C" int chatts_decoder_logprobs(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride, int k,
+                                       const int64_t* token, const int32_t* step_dev, int64_t out_stride, float* out_lp,
+                                       int32_t* out_rank, int32_t* out_top_ids, float* out_top_lp, chatts_stream_t stream) {
+  CHATTS_REQUIRE(d && logits && token && batch >= 1, CHATTS_E_BADARG, "decoder_logprobs: bad arguments");
+  const ChattsDecoderConfig& c = d->cfg;
+  // (the split-K / attention workspace is idle here, as for the selection ahead of this call)
+  if (c.tp_world <= 1)
+    return chatts_logprobs_batched(logits, batch, logits_stride, c.vocab_local, c.vocab_offset, k, token, step_dev, out_stride, out_lp,
+                                   out_rank, out_top_ids, out_top_lp, d->b.workspace, d->b.workspace_bytes, stream);
+  CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "decoder_logprobs: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", c.tp_world);
+  const int mb = d->b.max_batch > 0 ? d->b.max_batch : 1;
+  CHATTS_REQUIRE(batch <= mb, CHATTS_E_SHAPE, "decoder_logprobs: batch %d exceeds max_batch %d", batch, mb);
+  CHATTS_REQUIRE(d->b.logits_full, CHATTS_E_BADARG, "decoder_logprobs: logprobs under tensor parallelism need buffers.logits_full");
+  CHATTS_REQUIRE(logits_stride == c.vocab_local || batch == 1, CHATTS_E_SHAPE, "decoder_logprobs: logits rows must be contiguous");
+  // validate before the collective: a refusal on one rank must not leave the others waiting in it
+  CHATTS_REQUIRE(k >= 0 && k <= CHATTS_LOGPROBS_MAX_K && (k == 0 || (out_top_ids && out_top_lp)) && out_lp && out_rank, CHATTS_E_BADARG,
+                 "decoder_logprobs: k = %d / outputs", k);
+  int rc;
+  if ((rc = chatts_allgather(d->tp, logits, d->b.logits_full, batch, c.vocab_local, stream)) != 0) return rc;
+  const int64_t vfull = c.vocab_local * c.tp_world;
+  return chatts_logprobs_batched(d->b.logits_full, batch, vfull, vfull, 0, k, token, step_dev, out_stride, out_lp, out_rank, out_top_ids,
+                                 out_top_lp, d->b.workspace, d->b.workspace_bytes, stream);
+}
+
 extern "C" int chatts_decoder_select_sequence(ChattsDecoder* d, int seq) {
   CHATTS_REQUIRE(d && seq >= 0 && seq < (d->b.max_batch > 0 ? d->b.max_batch : 1), CHATTS_E_BADARG,
                  "decoder_select_sequence: slot %d out of range", seq);

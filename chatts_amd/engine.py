@@ -19,7 +19,7 @@ from collections import deque
 import numpy as np
 
 
-def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, **_):
+def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, logprobs=None, max_logprobs=20, prompt_logprobs=None, **_):
     """The ranges vLLM's SamplingParams accepts (what the reference's drivers pass: inference_tsmllm_vllm.py:43-46,
     llm_utils.py:153).  Raises ValueError - the server turns it into a 400 - BEFORE the request can reach the engine thread, where
     an out-of-range value would otherwise surface inside set_sampling / chatts_decoder_set_sampling."""
@@ -34,6 +34,11 @@ def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, **_):
         raise ValueError(f"top_k must be -1 / 0 (off) or positive, got {top_k}")
     if int(max_tokens) < 1:
         raise ValueError(f"max_tokens must be at least 1, got {max_tokens}")
+    if prompt_logprobs is not None:
+        raise ValueError("prompt_logprobs is not supported (only the logprobs of generated tokens)")
+    if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer))
+                                 or not 0 <= int(logprobs) <= int(max_logprobs)):
+        raise ValueError(f"logprobs must be an integer in 0..{max_logprobs} (max_logprobs), got {logprobs!r}")
 
 
 class ExchangeBroken(RuntimeError):
@@ -48,6 +53,8 @@ class Request:
         self.sampling_key, self.eos, self.on_tokens = sampling_key, set(eos or ()), on_tokens
         self.tokens, self.sent, self.finished, self.finish_reason = [], 0, False, None
         self.prompt_tokens = 0
+        # logprobs=k: one (logprob, rank, [(id, logprob)] * k) entry per token of `tokens`, grown with it; None when not asked
+        self.logprob_k, self.logprobs, self.cumulative_logprob = None, None, None
         self.t_arrival, self.t_first = time.perf_counter(), None
         self.error = None
         self.bypassed = 0                    # later arrivals admitted past this request while it waited for its sampling group
@@ -63,6 +70,7 @@ class Engine:
         # tensor-parallel group counts the same iterations (followers replay the leader's), so all of them switch together.
         self.greedy_return_steps = max(0, int(greedy_return_steps))
         self._greedy_iters = 0
+        self._no_logprob_iters = 0
         self.sync_every = max(1, int(sync_every))       # decode steps between device->host token reads
         # chunked-prefill scheduling (vLLM: enable_chunked_prefill / max_num_batched_tokens): while other sequences are decoding, a
         # long prompt is prefilled this many rows per scheduler iteration, each followed by one decode step of the running batch,
@@ -83,11 +91,13 @@ class Engine:
 
     # ---- requests ---------------------------------------------------------------------------------
     def add_request(self, prompt, timeseries=None, max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, seed=None,
-                    stop_token_ids=None, ignore_eos=False, on_tokens=None):
+                    stop_token_ids=None, ignore_eos=False, on_tokens=None, logprobs=None):
         """seed None: per-slot mode gives every request its own stream (a hash of its arrival number - vLLM's seed=None means "not
         reproducible across requests"; here two identical prompts still differ, and a rerun of the same arrival order repeats);
         grouped mode uses 0 (requests that decode together must share ONE configuration there)."""
-        validate_sampling(max_tokens, temperature, top_p, top_k)
+        validate_sampling(max_tokens, temperature, top_p, top_k, logprobs=logprobs, max_logprobs=self.max_logprobs)
+        if logprobs is not None and not hasattr(self.model, "set_logprobs"):
+            raise ValueError("this model does not compute logprobs")
         if seed is None:
             seed = ((self._rid + 1) * 2654435761) & 0xFFFFFFFF if self.mixed else 0
         e = self.model.config.eos_token_id
@@ -97,10 +107,35 @@ class Engine:
         self._rid += 1
         r = Request(self._rid, prompt, list(timeseries or []), max_tokens, key, eos, on_tokens)
         r.sampling = (0.0, 0, 1.0, 0) if key is None else key
+        if logprobs is not None:
+            r.logprob_k, r.logprobs, r.cumulative_logprob = int(logprobs), [], 0.0
         if self.mixed:
             r.sampling_key = "rows" if key is not None else None     # one group: who samples is a per-slot matter
         self.waiting.append(r)
         return r
+
+    @property
+    def max_logprobs(self):
+        return int(getattr(self.model, "max_logprobs", 20))
+
+    def _logprobs_mode(self):
+        """Logprobs on while any running, prefilling or waiting request asks for them; off again after `greedy_return_steps`
+        consecutive iterations without one (the sampling mode's hysteresis, for the same reason: a switch re-captures the graphs;
+        0 = stay on once on).  Followers replay the leader's requests and count the same iterations: all ranks switch together."""
+        if not hasattr(self.model, "set_logprobs"):
+            return
+        want = (any(r is not None and r.logprob_k is not None for r in self.slots) or
+                (self.prefilling is not None and self.prefilling[0].logprob_k is not None) or
+                any(q.logprob_k is not None for q in self.waiting))
+        on = bool(getattr(self.model, "_logprobs_on", False))
+        if want:
+            self._no_logprob_iters = 0
+            if not on:
+                self.model.set_logprobs(True)
+        elif on:
+            self._no_logprob_iters += 1
+            if self.greedy_return_steps and self._no_logprob_iters >= self.greedy_return_steps:
+                self.model.set_logprobs(False)
 
     def has_work(self):
         return bool(self.waiting) or self.prefilling is not None or any(s is not None for s in self.slots)
@@ -159,6 +194,7 @@ class Engine:
         running = any(s is not None for s in self.slots) or self.prefilling is not None
         if self.mixed:
             self._mixed_mode()
+        self._logprobs_mode()
         while not self.mixed and not running and self.waiting and self.waiting[0].sampling_key != self.active_key:
             try:
                 self._apply_sampling(self.waiting[0].sampling_key)
@@ -319,14 +355,25 @@ class Engine:
                 r.t_first = time.perf_counter()
             if cut is not None:
                 r.tokens = toks[:cut]
+                self._read_logprobs(s, r)
                 self._retire(s, "stop", done)
             elif self.produced[s] >= r.max_tokens:
                 r.tokens = toks[:r.max_tokens]
+                self._read_logprobs(s, r)
                 self._retire(s, "length", done)
             else:
                 r.tokens = toks
+                self._read_logprobs(s, r)
                 self._emit(r, False)
         return done
+
+    def _read_logprobs(self, s, r):
+        """the entries of the tokens read in this harvest (requests that asked only)"""
+        if r.logprob_k is None or len(r.logprobs) >= len(r.tokens):
+            return
+        new = self.model.read_logprobs(s, len(r.logprobs), len(r.tokens), r.logprob_k)
+        r.logprobs.extend(new)
+        r.cumulative_logprob = float(sum(e[0] for e in r.logprobs))
 
     def _retire(self, s, reason, done):
         r = self.slots[s]
@@ -463,7 +510,8 @@ class EngineThread:
         ok = []
         for kw in new:
             try:
-                validate_sampling(**{k: kw[k] for k in ("max_tokens", "temperature", "top_p", "top_k") if k in kw})
+                validate_sampling(**{k: kw[k] for k in ("max_tokens", "temperature", "top_p", "top_k", "logprobs") if k in kw},
+                                  max_logprobs=getattr(self.engine, "max_logprobs", 20))
                 ok.append(kw)
             except (ValueError, TypeError) as e:
                 r = Request(-1, kw.get("prompt"), list(kw.get("timeseries") or []), 1, None, [], kw.get("on_tokens"))

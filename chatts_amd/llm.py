@@ -11,7 +11,12 @@ import numpy as np
 
 class SamplingParams:
     def __init__(self, max_tokens=16, temperature=0.0, top_p=1.0, top_k=-1, seed=None, stop_token_ids=None,
-                 ignore_eos=False, **kw):
+                 ignore_eos=False, logprobs=None, prompt_logprobs=None, **kw):
+        if prompt_logprobs is not None:
+            raise ValueError("prompt_logprobs is not supported (only the logprobs of generated tokens: logprobs=k)")
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or logprobs < 0):
+            raise ValueError(f"logprobs must be a non-negative integer, got {logprobs!r}")
+        self.logprobs = logprobs                # k: the chosen token + its k best alternatives per generated token (raw logits)
         self.max_tokens = int(max_tokens)
         self.temperature = temperature          # 0 = greedy (this engine's default; the reference's drivers pass 0.2 / 0.5)
         self.top_p = top_p
@@ -21,9 +26,35 @@ class SamplingParams:
         self.ignore_eos = ignore_eos
 
 
+class Logprob:
+    """vLLM's Logprob: log-probability of a token under the raw logits of its step, its 1-based rank, its text"""
+
+    def __init__(self, logprob, rank=None, decoded_token=None):
+        self.logprob, self.rank, self.decoded_token = logprob, rank, decoded_token
+
+    def __repr__(self):
+        return f"Logprob(logprob={self.logprob}, rank={self.rank}, decoded_token={self.decoded_token!r})"
+
+
 class CompletionOutput:
-    def __init__(self, text, token_ids):
+    def __init__(self, text, token_ids, logprobs=None, cumulative_logprob=None):
         self.text, self.token_ids, self.index = text, token_ids, 0
+        # logprobs: one {token_id: Logprob} per generated token (its top-k + the chosen token); None when not requested
+        self.logprobs, self.cumulative_logprob = logprobs, cumulative_logprob
+
+
+def _logprob_dicts(tokenizer, token_ids, entries):
+    out = []
+    for tid, (lp, rank, top) in zip(token_ids, entries):
+        d = {}
+        for r, (i, v) in enumerate(top):
+            d[int(i)] = Logprob(v, r + 1, tokenizer.decode([int(i)], skip_special_tokens=False))
+        if int(tid) not in d:
+            d[int(tid)] = Logprob(lp, rank, tokenizer.decode([int(tid)], skip_special_tokens=False))
+        else:
+            d[int(tid)] = Logprob(lp, rank, d[int(tid)].decoded_token)
+        out.append(d)
+    return out
 
 
 class RequestOutput:
@@ -54,7 +85,7 @@ def _build_llm(model, kw):
 class LLM:
     def __init__(self, model, tensor_parallel_size=1, max_model_len=6000, limit_mm_per_prompt=None,
                  trust_remote_code=True, gpu_memory_utilization=None, seed=0, tokenizer=None, comm=None,
-                 max_num_seqs=1, block_size=None, num_gpu_blocks_override=None, kv_cache_dtype=None, **kw):
+                 max_num_seqs=1, block_size=None, num_gpu_blocks_override=None, kv_cache_dtype=None, max_logprobs=20, **kw):
         from .config import PRESETS, ChatTSConfig, preset
         from .modeling import ChatTSForCausalLM
         from .processing import ChatTSProcessor
@@ -70,7 +101,7 @@ class LLM:
                             limit_mm_per_prompt=limit_mm_per_prompt, trust_remote_code=trust_remote_code,
                             gpu_memory_utilization=gpu_memory_utilization, seed=seed, tokenizer=tokenizer,
                             max_num_seqs=max_num_seqs, block_size=block_size, num_gpu_blocks_override=num_gpu_blocks_override,
-                            kv_cache_dtype=kv_cache_dtype, **kw)
+                            kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs, **kw)
                 group, inner = TpGroup.launch(tensor_parallel_size, _build_llm, (model, args))
                 self.__dict__.update(inner.__dict__)
                 self._tp_group = group
@@ -87,7 +118,7 @@ class LLM:
         # kv_cache_dtype (vLLM's name): None / "auto" = the float32 KV cache, "fp16" = the half-size speed mode (ChatTSForCausalLM)
         mk = dict(comm=comm, max_ctx=max_model_len, max_prefill_tokens=min(2048, max_model_len),
                   max_batch=max(1, int(max_num_seqs)), kv_block_size=block_size, kv_pool_blocks=num_gpu_blocks_override,
-                  kv_cache_dtype=kv_cache_dtype)
+                  kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs)
         if isinstance(model, ChatTSConfig):
             self.model = ChatTSForCausalLM.from_synthetic(model, seed=seed, **mk)
         elif isinstance(model, str) and model in PRESETS:
@@ -121,6 +152,9 @@ class LLM:
         if self._tp_group is not None:      # spawned followers run the same call now; all ranks meet inside the exchange kernels
             self._tp_group.call("generate", prompts, sampling_params)
         sp = sampling_params or SamplingParams()
+        if sp.logprobs is not None and sp.logprobs > self.model.max_logprobs:
+            raise ValueError(f"logprobs={sp.logprobs} exceeds max_logprobs={self.model.max_logprobs} (LLM(max_logprobs=...))")
+        self.model.set_logprobs(sp.logprobs is not None)      # per call, like the sampling mode (a switch re-captures the graphs)
         self.model.set_sampling(sp.temperature or 0.0, max(int(sp.top_k or 0), 0), sp.top_p,
                                 self._seed if sp.seed is None else sp.seed)
         if isinstance(prompts, (str, dict)):
@@ -140,7 +174,12 @@ class LLM:
             metas.append((req["prompt"], ids))
         e = self.config.eos_token_id
         eos = None if sp.ignore_eos else ((list(e) if isinstance(e, (list, tuple)) else [e]) + sp.stop_token_ids)
-        toks_all = self.model.generate_batch(reqs, sp.max_tokens, eos)      # sequential when max_num_seqs == 1
         tok = self.processor.tokenizer
-        return [RequestOutput(p, ids, [CompletionOutput(tok.decode(t, skip_special_tokens=True), t)])
-                for (p, ids), t in zip(metas, toks_all)]
+        if sp.logprobs is None:
+            toks_all = self.model.generate_batch(reqs, sp.max_tokens, eos)      # sequential when max_num_seqs == 1
+            return [RequestOutput(p, ids, [CompletionOutput(tok.decode(t, skip_special_tokens=True), t)])
+                    for (p, ids), t in zip(metas, toks_all)]
+        toks_all, entries_all = self.model.generate_batch(reqs, sp.max_tokens, eos, logprobs=sp.logprobs)
+        return [RequestOutput(p, ids, [CompletionOutput(tok.decode(t, skip_special_tokens=True), t, _logprob_dicts(tok, t, e),
+                                                        float(sum(x[0] for x in e)))])
+                for (p, ids), t, e in zip(metas, toks_all, entries_all)]

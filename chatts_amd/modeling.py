@@ -111,8 +111,10 @@ class ChatTSForCausalLM:
 
     def __init__(self, config, device="cuda", comm=None, max_ctx=2048, max_prefill_tokens=2048, use_graph=True,
                  max_batch=1, weight_format="bf16", use_p2p=True, enable_prefix_caching=True, kv_block_size=None,
-                 kv_pool_blocks=None, precision=None, prefill_tiled_weights=None, kv_cache_dtype=None):
+                 kv_pool_blocks=None, precision=None, prefill_tiled_weights=None, kv_cache_dtype=None, max_logprobs=20):
         kv_name = kv_cache_dtype_name(kv_cache_dtype)       # (checked before anything touches the device)
+        if not 0 <= int(max_logprobs) <= _lib.LOGPROBS_MAX_K:
+            raise ValueError(f"max_logprobs={max_logprobs} must be in 0..{_lib.LOGPROBS_MAX_K}")
         if not torch.cuda.is_available():
             raise RuntimeError("chatts_amd needs a ROCm GPU: there is no CPU fallback for the model")
         self.lib = _lib.load()
@@ -187,6 +189,10 @@ class ChatTSForCausalLM:
         self._tensors = {}            # keeps every device tensor alive (the C side borrows pointers)
         self._decoder = None
         self._graph = None
+        # token logprobs (set_logprobs): every selection is followed by chatts_decoder_logprobs with K = max_logprobs into per-slot
+        # rings [max_batch, out_stride(, K)] allocated on first use; a request reads the first k <= max_logprobs of its cells
+        self.max_logprobs = int(max_logprobs)
+        self._logprobs_on = False
         self.layers = []
         self.loaded = set()
 
@@ -378,6 +384,7 @@ class ChatTSForCausalLM:
         for m in range(2, self.max_batch + 1):     # batched lm_head
             ws_bytes = max(ws_bytes, int(lib.chatts_linear_workspace(m, plan.vocab, H)))
         ws_bytes = max(ws_bytes, int(lib.chatts_attn_workspace(self.max_batch, plan.nq, self.n_splits)) + 256)
+        ws_bytes = max(ws_bytes, int(lib.chatts_logprobs_workspace(max(1, self.max_batch), self.max_logprobs)))
         # the prefill attention's K / V planes (kv_planes_kernel: 32 KB per (kv head, 32-key tile)) for a sequence of max_ctx positions:
         # with the workspace sized for them the planes kernel is taken at EVERY chunk position, so the same prompt never changes
         # kernel (and summation order) with where a chunk starts
@@ -853,6 +860,61 @@ class ChatTSForCausalLM:
         s32 = int(seed) & 0xFFFFFFFF
         B["samp_seed"][slot] = s32 - (1 << 32) if s32 >= (1 << 31) else s32
 
+    def set_logprobs(self, on):
+        """Token logprobs on / off for every following selection.  On: each selection (decode steps, first tokens of every admission
+        path) is followed by chatts_decoder_logprobs into the per-slot rings - log_softmax of the raw logits, the chosen token's rank and
+        the max_logprobs best alternatives.  A switch drops the captured decode graphs (like a sampling-mode change); off, the steps are
+        exactly what they are without the feature.  generate_one / generate_batch switch it on when asked and leave it on; the engine
+        switches it off after greedy_return_steps iterations without a requester."""
+        on = bool(on)
+        if on == self._logprobs_on:
+            return
+        if on and self.plan.world > 1 and self._tp is None and self.max_batch > 1:
+            raise NotImplementedError("logprobs under tensor parallelism need the peer-to-peer exchange (use_p2p=True) for batched decode")
+        if on:
+            self._logprob_rings()
+        self._logprobs_on = on
+        self._graph = None
+        self._graph_batched = None
+
+    def _logprob_rings(self):
+        if "lp" not in self.buf:
+            B, dev, n = self.buf, self.device, max(1, self.max_batch)
+            S, K = B["out_tokens_all"].shape[1], self.max_logprobs
+            B["lp"] = torch.full((n, S), float("nan"), dtype=torch.float32, device=dev)
+            B["lp_rank"] = torch.zeros((n, S), dtype=torch.int32, device=dev)
+            B["lp_top_ids"] = torch.full((n, S, max(K, 1)), -1, dtype=torch.int32, device=dev)
+            B["lp_top_lp"] = torch.full((n, S, max(K, 1)), float("nan"), dtype=torch.float32, device=dev)
+        B = self.buf
+        return {"lp": B["lp"], "rank": B["lp_rank"], "top_ids": B["lp_top_ids"], "top_lp": B["lp_top_lp"], "stride": B["lp"].shape[1]}
+
+    def _logprobs_after(self, logits, batch, slot):
+        """(logprobs on) the cells of the tokens the selection just wrote for slots slot .. slot + batch - 1"""
+        if not self._logprobs_on:
+            return
+        B, R = self.buf, self._logprob_rings()
+        S, K = R["stride"], self.max_logprobs
+        _lib.check(self.lib.chatts_decoder_logprobs(
+            self._decoder, _lib.ptr(logits), batch, self.plan.vocab, K, B["token_all"][slot:].data_ptr(), B["step_all"][slot:].data_ptr(),
+            S, R["lp"][slot:].data_ptr(), R["rank"][slot:].data_ptr(), R["top_ids"][slot:].data_ptr(), R["top_lp"][slot:].data_ptr(),
+            _lib.stream_ptr()))
+
+    def read_logprobs(self, slot, start, stop, k):
+        """Host entries of cells [start, stop) of a slot: one (logprob, rank, [(id, logprob)] * k) per generated token."""
+        k = int(k)
+        if not self._logprobs_on and "lp" not in self.buf:
+            raise RuntimeError("logprobs were not turned on (set_logprobs)")
+        if stop <= start:
+            return []
+        if k > self.max_logprobs:
+            raise ValueError(f"logprobs={k} exceeds max_logprobs={self.max_logprobs}")
+        R = self._logprob_rings()
+        lp = R["lp"][slot, start:stop].tolist()
+        rank = R["rank"][slot, start:stop].tolist()
+        ids = R["top_ids"][slot, start:stop, :k].tolist() if k else [[] for _ in lp]
+        tlp = R["top_lp"][slot, start:stop, :k].tolist() if k else [[] for _ in lp]
+        return [(a, b, list(zip(i, v))) for a, b, i, v in zip(lp, rank, ids, tlp)]
+
     def _select_token(self):
         """logits of this rank -> next token in B['token'] (appended to out_tokens, step bumped) on every rank: greedy or the
         configured sampler, agreed across TP ranks by chatts_decoder_select_tokens ((max, idx) pairs / gathered logits)."""
@@ -861,7 +923,19 @@ class ChatTSForCausalLM:
             _lib.check(lib.chatts_decoder_select_tokens(self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, _lib.ptr(B["token"]),
                                                         _lib.ptr(B["token_logit"]), _lib.ptr(B["out_tokens"]), 0,
                                                         _lib.ptr(B["step"]), None, 0, None, st))
+            self._logprobs_after(B["logits"], 1, 0)
             return
+        self._select_token_host_tp()
+        if self._logprobs_on:     # every rank: the same kernel on the same gathered logits
+            full = self.comm.all_gather_cat(B["logits"])
+            R = self._logprob_rings()
+            _lib.check(lib.chatts_logprobs_batched(_lib.ptr(full), 1, full.numel(), full.numel(), 0, self.max_logprobs,
+                                                   _lib.ptr(B["token"]), _lib.ptr(B["step"]), R["stride"], _lib.ptr(R["lp"]),
+                                                   _lib.ptr(R["rank"]), _lib.ptr(R["top_ids"]), _lib.ptr(R["top_lp"]),
+                                                   _lib.ptr(B["ws"]), B["ws"].numel(), st))
+
+    def _select_token_host_tp(self):
+        lib, st, B = self.lib, _lib.stream_ptr(), self.buf
         # TP without the peer-to-peer exchange (use_p2p=False): host-driven RCCL gathers
         sa = getattr(self, "_sampling", None)
         if sa is None:      # greedy: one (logit, index) pair per rank instead of the [V / W] logits
@@ -894,6 +968,7 @@ class ChatTSForCausalLM:
             _lib.check(lib.chatts_decoder_decode_step(self._decoder, _lib.ptr(B["pos"]), _lib.ptr(B["step"]),
                                                       _lib.ptr(B["token"]), _lib.ptr(B["token_logit"]),
                                                       _lib.ptr(B["out_tokens"]), self.n_splits, st))
+            self._logprobs_after(B["logits"], 1, 0)
             return
         self._run_layers(1, 0, pos_dev=B["pos"], n_splits=self.n_splits)
         _lib.check(lib.chatts_decoder_logits(self._decoder, 0, st))
@@ -962,6 +1037,7 @@ class ChatTSForCausalLM:
             self._decoder, self.max_batch, _lib.ptr(B["pos_all"]), _lib.ptr(B["step_all"]), _lib.ptr(B["token_all"]),
             _lib.ptr(B["token_logit_all"]), _lib.ptr(B["out_tokens_all"]), B["out_tokens_all"].shape[1],
             _lib.ptr(B["logits_all"]), self._n_splits_batched(), _lib.stream_ptr()))
+        self._logprobs_after(B["logits_all"], self.max_batch, 0)
 
     def batched_step(self):
         """One greedy token for EVERY cache slot (idle slots compute harmlessly; their position saturates)."""
@@ -1171,6 +1247,7 @@ class ChatTSForCausalLM:
             self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
             B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), B["out_tokens_all"].shape[1],
             B["step_all"][slot:].data_ptr(), None, 0, None if sa1 is None else C.byref(sa1), st))
+        self._logprobs_after(B["logits"], 1, slot)
 
     def plan_pack(self, candidates, free_slots):
         """Which of the waiting requests should be prefilled TOGETHER (chatts_decoder_prefill_packed).  candidates: list of
@@ -1287,16 +1364,30 @@ class ChatTSForCausalLM:
         return Ts
 
     @torch.no_grad()
-    def generate_batch(self, requests, max_new_tokens=64, eos_token_id=None, sync_every=8):
+    def generate_batch(self, requests, max_new_tokens=64, eos_token_id=None, sync_every=8, logprobs=None):
         """Continuous batching over `max_batch` cache slots.  requests: list of (ids, series [n,2Lmax,1] | None,
         lengths | None).  A finished sequence frees its slot for the next waiting request at the next sync point.
-        Returns the list of generated token lists, in request order."""
+        Returns the list of generated token lists, in request order.  logprobs: k for every request, or a list with one k / None per
+        request -> (token lists, entry lists) (entries as in generate_one; None for a request that did not ask)."""
+        ks = list(logprobs) if isinstance(logprobs, (list, tuple)) else [logprobs] * len(requests)
+        if len(ks) != len(requests):
+            raise ValueError("logprobs: one value per request")
+        for k in ks:
+            if k is not None:
+                self._check_logprobs(k)
+        want = any(k is not None for k in ks)
+        if want:
+            self.set_logprobs(True)
         if self.max_batch < 2:
-            return [self.generate_one(i, s, l, max_new_tokens, eos_token_id) for (i, s, l) in requests]
+            outs = [self.generate_one(i, s, l, max_new_tokens, eos_token_id, logprobs=k) for (i, s, l), k in zip(requests, ks)]
+            if logprobs is None:
+                return outs
+            return [o[0] if k is not None else o for o, k in zip(outs, ks)], [o[1] if k is not None else None for o, k in zip(outs, ks)]
         eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple, set)) else
                   ([] if eos_token_id is None else [eos_token_id]))
         B = self.buf
         results = [None] * len(requests)
+        entries = [None] * len(requests)
         waiting = list(range(len(requests)))[::-1]
         slots = [None] * self.max_batch              # request index per slot
         produced = [0] * self.max_batch
@@ -1314,6 +1405,8 @@ class ChatTSForCausalLM:
                 cut = next((i + 1 for i, t in enumerate(toks) if t in eos), None) if eos else None
                 if cut is not None or produced[s] >= max_new_tokens or final:
                     results[r] = toks[:cut] if cut is not None else toks[:max_new_tokens]
+                    if ks[r] is not None:
+                        entries[r] = self.read_logprobs(s, 0, len(results[r]), ks[r])
                     slots[s] = None
                     B["pos_all"][s] = -1         # parked: the batched step neither attends nor writes this slot's cache
                     self.note_generated(s, results[r])
@@ -1371,7 +1464,7 @@ class ChatTSForCausalLM:
             if steps_since_sync >= sync_every or all(r is None or produced[s] >= max_new_tokens for s, r in enumerate(slots)):
                 harvest()
                 steps_since_sync = 0
-        return results
+        return (results, entries) if logprobs is not None else results
 
     # ---------------------------------------------------------------------------------------------
     # HF surface
@@ -1396,8 +1489,13 @@ class ChatTSForCausalLM:
 
     @torch.no_grad()
     def generate_one(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, sync_every=16,
-                     return_logits=False):
-        """ids: un-expanded prompt ids (host list); series: [n, 2*Lmax, 1] tensor of this prompt's series."""
+                     return_logits=False, logprobs=None):
+        """ids: un-expanded prompt ids (host list); series: [n, 2*Lmax, 1] tensor of this prompt's series.
+        logprobs=k (0 <= k <= max_logprobs): also return one (logprob, rank, top-k [(id, logprob)]) entry per returned token, last in
+        the result tuple (toks[, logits0], entries)."""
+        if logprobs is not None:
+            self._check_logprobs(logprobs)
+            self.set_logprobs(True)
         self._prefill_request(ids, series, lengths, max_new_tokens)
         logits0 = self.buf["logits"].clone() if return_logits else None
         eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple, set)) else
@@ -1420,7 +1518,12 @@ class ChatTSForCausalLM:
                     toks = toks[:i + 1]
                     break
         self.note_generated(0, toks)
-        return (toks, logits0) if return_logits else toks
+        out = (toks,) + ((logits0,) if return_logits else ()) + ((self.read_logprobs(0, 0, len(toks), logprobs),) if logprobs is not None else ())
+        return out[0] if len(out) == 1 else out
+
+    def _check_logprobs(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= self.max_logprobs:
+            raise ValueError(f"logprobs={k!r} must be an integer in 0..max_logprobs={self.max_logprobs}")
 
     @torch.no_grad()
     def generate_stream(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, chunk=1):

@@ -89,6 +89,57 @@ def sampling_from_body(body, default_max_tokens=512):
     return out
 
 
+def logprobs_from_body(body, chat, max_logprobs=20):
+    """the request's logprobs k (0 <= k <= max_logprobs) or None.  Chat: `logprobs: true` + `top_logprobs: k` (0 when absent);
+    completions: `logprobs: k`.  Malformed / out-of-range values and top_logprobs without logprobs raise ValueError (-> 400)."""
+    def count(name, v):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= max_logprobs:
+            raise ValueError(f"{name} must be an integer in 0..{max_logprobs}, got {v!r}")
+        return v
+    if body.get("prompt_logprobs") is not None:
+        raise ValueError("prompt_logprobs is not supported")
+    lp = body.get("logprobs")
+    if chat:
+        top = body.get("top_logprobs")
+        if lp is not None and not isinstance(lp, bool):
+            raise ValueError(f"logprobs must be a boolean, got {lp!r}")
+        if not lp:
+            if top is not None:
+                raise ValueError("top_logprobs needs logprobs: true")
+            return None
+        return 0 if top is None else count("top_logprobs", top)
+    return None if lp is None else count("logprobs", lp)
+
+
+def _token_piece(tokenizer, tid):
+    return tokenizer.decode([int(tid)], skip_special_tokens=False)
+
+
+def chat_logprobs_content(tokenizer, token_ids, entries, k):
+    """-> the `content` list of an OpenAI chat choice's `logprobs` for these tokens and their engine entries"""
+    out = []
+    for tid, (lp, _rank, top) in zip(token_ids, entries):
+        t = _token_piece(tokenizer, tid)
+        out.append({"token": t, "logprob": lp, "bytes": list(t.encode("utf-8")),
+                    "top_logprobs": [{"token": (p := _token_piece(tokenizer, i)), "logprob": v, "bytes": list(p.encode("utf-8"))}
+                                     for i, v in top[:k]]})
+    return out
+
+
+def completion_logprobs(tokenizer, token_ids, entries, k, offset0=0):
+    """-> an OpenAI completions choice's `logprobs` ({tokens, token_logprobs, top_logprobs, text_offset}) for these tokens"""
+    d = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+    off = offset0
+    for tid, (lp, _rank, top) in zip(token_ids, entries):
+        t = _token_piece(tokenizer, tid)
+        d["tokens"].append(t)
+        d["token_logprobs"].append(lp)
+        d["top_logprobs"].append({_token_piece(tokenizer, i): v for i, v in top[:k]})
+        d["text_offset"].append(off)
+        off += len(t)
+    return d
+
+
 class IncrementalDecoder:
     """token ids -> text deltas.  Decodes the whole sequence each time and emits the new suffix, holding back a trailing
     replacement character (an incomplete multi-byte piece), like vLLM's incremental detokenizer."""
@@ -109,7 +160,7 @@ class IncrementalDecoder:
 # ---------------------------------------------------------------------------------------------------------------
 # the app
 # ---------------------------------------------------------------------------------------------------------------
-def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_timeseries=15, default_max_tokens=512):
+def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_timeseries=15, default_max_tokens=512, max_logprobs=20):
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse, StreamingResponse
     app = FastAPI(title="chatts_amd")
@@ -163,6 +214,9 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
             if len(series) > limit_timeseries:
                 raise ValueError(f"At most {limit_timeseries} timeseries may be provided in one prompt, got {len(series)}")
             sp = sampling_from_body(body, default_max_tokens)
+            lpk = logprobs_from_body(body, chat, max_logprobs)
+            if lpk is not None:                  # (only then: an engine without logprobs never sees the keyword)
+                sp["logprobs"] = lpk
         except (ValueError, TypeError, KeyError) as e:
             return error(400, str(e))
         rid = ("chatcmpl-" if chat else "cmpl-") + uuid.uuid4().hex[:24]
@@ -173,8 +227,22 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
         except RuntimeError as e:
             return error(500, str(e), "server_error")
         dec = IncrementalDecoder(tokenizer)
+        lp_state = {"n": 0, "offset": 0}               # tokens whose entries were delivered; completions' text_offset so far
 
-        def chunk(delta_text, finish=None, first=False):
+        def lp_part(new, r):
+            """the choice's `logprobs` for the tokens `new` just delivered (None when the request did not ask)"""
+            if lpk is None:
+                return None
+            n = lp_state["n"]
+            entries = list(r.logprobs[n:n + len(new)])
+            lp_state["n"] = n + len(new)
+            if chat:
+                return {"content": chat_logprobs_content(tokenizer, new, entries, lpk)}
+            d = completion_logprobs(tokenizer, new, entries, lpk, lp_state["offset"])
+            lp_state["offset"] += sum(len(t) for t in d["tokens"])
+            return d
+
+        def chunk(delta_text, finish=None, first=False, logprobs=None):
             if chat:
                 delta = {"content": delta_text} if delta_text or not first else {}
                 if first:
@@ -182,6 +250,8 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
                 ch = {"index": 0, "delta": delta, "finish_reason": finish}
             else:
                 ch = {"index": 0, "text": delta_text, "finish_reason": finish}
+            if logprobs is not None:
+                ch["logprobs"] = logprobs
             return {"id": rid, "object": obj + ".chunk" if chat else obj, "created": int(time.time()), "model": model_name, "choices": [ch]}
 
         if body.get("stream"):
@@ -197,8 +267,9 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
                         yield "data: " + json.dumps({"error": {"message": str(r.error), "type": "invalid_request_error"}}) + "\n\n"
                         break
                     text = dec.push(new, final=finished)
-                    if text or first:
-                        yield "data: " + json.dumps(chunk(text, None, first)) + "\n\n"
+                    part = lp_part(new, r) if new else None
+                    if text or first or part is not None:
+                        yield "data: " + json.dumps(chunk(text, None, first, part)) + "\n\n"
                         first = False
                     if finished:
                         yield "data: " + json.dumps(chunk("", r.finish_reason)) + "\n\n"
@@ -215,11 +286,14 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
             dec.push(new, final=finished)
             if finished:
                 break
+        lp_all = lp_part(list(r.tokens), r)
         usage = {"prompt_tokens": r.prompt_tokens, "completion_tokens": len(r.tokens), "total_tokens": r.prompt_tokens + len(r.tokens)}
         if chat:
             choice = {"index": 0, "message": {"role": "assistant", "content": dec.text}, "finish_reason": r.finish_reason}
         else:
             choice = {"index": 0, "text": dec.text, "finish_reason": r.finish_reason}
+        if lp_all is not None:
+            choice["logprobs"] = lp_all
         return {"id": rid, "object": obj, "created": int(time.time()), "model": model_name, "choices": [choice], "usage": usage,
                 "token_ids": list(r.tokens)}
 
@@ -244,7 +318,7 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
 
 def build_server(model, tensor_parallel_size=1, max_model_len=6000, max_num_seqs=1, seed=0, tokenizer=None,
                  served_model_name="chatts", limit_timeseries=15, block_size=None, num_gpu_blocks_override=None,
-                 enable_chunked_prefill=False, max_num_batched_tokens=512, kv_cache_dtype=None):
+                 enable_chunked_prefill=False, max_num_batched_tokens=512, kv_cache_dtype=None, max_logprobs=20):
     """LLM (model + processor) -> Engine -> EngineThread -> FastAPI app.
     Tensor parallel (one process per GPU under torchrun, process group initialised): rank 0 gets the app, the other ranks get
     None after serving as followers until the leader shuts down (engine.follow)."""
@@ -252,14 +326,14 @@ def build_server(model, tensor_parallel_size=1, max_model_len=6000, max_num_seqs
     from .llm import LLM
     llm = LLM(model, tensor_parallel_size=tensor_parallel_size, max_model_len=max_model_len, max_num_seqs=max_num_seqs, seed=seed,
               tokenizer=tokenizer, limit_mm_per_prompt={"timeseries": limit_timeseries}, block_size=block_size,
-              num_gpu_blocks_override=num_gpu_blocks_override, kv_cache_dtype=kv_cache_dtype)
+              num_gpu_blocks_override=num_gpu_blocks_override, kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs)
     control = ControlPlane.create() if tensor_parallel_size > 1 else None
     engine = Engine(llm.model, llm.processor, prefill_chunk_tokens=max_num_batched_tokens if enable_chunked_prefill else None)
     if control is not None and control.rank != 0:
         follow(engine, control)                  # returns when the leader publishes the shutdown
         return None
     et = EngineThread(engine, device=llm.model.device, control=control)
-    app = create_app(et, llm.processor.tokenizer, served_model_name, limit_timeseries)
+    app = create_app(et, llm.processor.tokenizer, served_model_name, limit_timeseries, max_logprobs=max_logprobs)
     app.state.engine_thread, app.state.llm = et, llm
     return app
 
@@ -284,6 +358,7 @@ def main():
                     "max-num-seqs x max-model-len / block-size oversubscribes the slots)")
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp16"], default="auto", help="auto: the float32 KV cache (parity grade); "
                     "fp16: half the cache bytes, logits ~2e-3 of the float32 oracle (speed mode)")
+    ap.add_argument("--max-logprobs", type=int, default=20, help="largest logprobs / top_logprobs a request may ask for (0..64)")
     args = ap.parse_args()
     limit = int(dict(kv.split("=") for kv in args.limit_mm_per_prompt.split(",")).get("timeseries", 15))
     import uvicorn
@@ -300,7 +375,8 @@ def main():
     app = build_server(args.model, args.tensor_parallel_size, args.max_model_len, args.max_num_seqs, args.seed,
                        served_model_name=args.served_model_name, limit_timeseries=limit, block_size=args.block_size,
                        num_gpu_blocks_override=args.num_gpu_blocks_override, enable_chunked_prefill=args.enable_chunked_prefill,
-                       max_num_batched_tokens=args.max_num_batched_tokens, kv_cache_dtype=args.kv_cache_dtype)
+                       max_num_batched_tokens=args.max_num_batched_tokens, kv_cache_dtype=args.kv_cache_dtype,
+                       max_logprobs=args.max_logprobs)
     if app is None:
         return                                   # a follower rank: the leader has shut down
     try:

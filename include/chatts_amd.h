@@ -474,6 +474,26 @@ int chatts_sample_batched(const float* logits, int batch, int64_t logits_stride,
                           const ChattsSamplingArgs* args, int64_t* token, float* token_logit, int64_t* out_tokens,
                           int64_t out_stride, int32_t* step_dev, int32_t* pos_dev, int pos_limit, chatts_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Logprobs of chosen tokens (vLLM V1's raw_logprobs: log_softmax of the raw logits, before temperature / top-k / top-p).
+ * Call after a selection (chatts_argmax_batched / chatts_sample_batched / chatts_decoder_select_tokens) on the same logits: row b
+ * reads token[b] (a global id; local index token[b] - vocab_offset) and its draw counter step_dev[b], which the selection has
+ * already bumped, and writes cell [b, step_dev[b] - 1] - the cell out_tokens received (cell 0 when step_dev is NULL), nothing when
+ * that cell is negative or >= out_stride (out_stride 0: unbounded, batch 1 only):
+ *   out_lp[cell]       = l_tok - lse, lse = m + log(sum_j exp(l_j - m)) over the `vocab` logits (NaN when the token is not in them)
+ *   out_rank[cell]     = 1 + #{l_j > l_tok} + #{j < tok : l_j == l_tok}: the 1-based position in (logit desc, id asc) order
+ *   out_top_ids/lp[cell * k + j], j < k: the k first (global id, logprob) pairs in that order (-1 / -inf past the vocabulary)
+ * cell = b * out_stride + step_dev[b] - 1.  0 <= k <= CHATTS_LOGPROBS_MAX_K; the top-K outputs may be NULL when k == 0.
+ * vocab <= 262144.  Two launches (partials of <= 64 slices per row, one merging wave per row); fixed reduction shapes, so the same
+ * logits give the same bits.  Needs >= chatts_logprobs_workspace(batch, k) bytes of device scratch; graph-capturable.
+ * ------------------------------------------------------------------------------------------- */
+#define CHATTS_LOGPROBS_MAX_K 64
+size_t chatts_logprobs_workspace(int batch, int k);
+int chatts_logprobs_batched(const float* logits, int batch, int64_t logits_stride, int64_t vocab, int64_t vocab_offset, int k,
+                            const int64_t* token, const int32_t* step_dev, int64_t out_stride, float* out_lp, int32_t* out_rank,
+                            int32_t* out_top_ids, float* out_top_lp, void* workspace, size_t workspace_bytes,
+                            chatts_stream_t stream);
+
 /* x[h] = float(table[*token - vocab_offset, h]) : next-step input embedding, token id read on the device. */
 int chatts_embed_token(const int64_t* token_dev, const chatts_bf16* table, int64_t vocab_offset,
                        int64_t vocab_rows, int hidden, float* out, chatts_stream_t stream);
@@ -711,6 +731,13 @@ int chatts_decoder_select_tokens(ChattsDecoder*, const float* logits, int batch,
                                  float* token_logit, int64_t* out_tokens, int64_t out_stride, int32_t* step_dev,
                                  int32_t* pos_dev, int pos_limit, const ChattsSamplingArgs* override_or_null,
                                  chatts_stream_t stream);
+
+/* chatts_logprobs_batched for `batch` rows of this rank's logits, after chatts_decoder_select_tokens chose their tokens, on the
+ * decoder's idle workspace.  Under tensor parallelism the logits are gathered into buffers.logits_full (chatts_allgather) and every
+ * rank runs the kernel on the full vocabulary: identical results on every rank.  Graph-capturable. */
+int chatts_decoder_logprobs(ChattsDecoder*, const float* logits, int batch, int64_t logits_stride, int k, const int64_t* token,
+                            const int32_t* step_dev, int64_t out_stride, float* out_lp, int32_t* out_rank, int32_t* out_top_ids,
+                            float* out_top_lp, chatts_stream_t stream);
 
 /* Token selection of chatts_decoder_decode_step(_batched): NULL (default) = greedy argmax; otherwise the sampler above
  * with these parameters (copied).  Changing it invalidates any hipGraph captured over a decode step. */
