@@ -17,12 +17,13 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, synth
+from . import _lib, prefix_cache, synth
 from .config import ChatTSConfig, preset
 from .tp import Comm, LocalComm, ShardPlan
 from .ts_encoder import TimeSeriesEmbedding
 
 packed_modules_mapping = {"qkv_proj": ["q_proj", "k_proj", "v_proj"], "gate_up_proj": ["gate_proj", "up_proj"]}
+PROJECTIONS = ("qkv", "o", "gate_up", "down")          # the four weight matrices of a layer, as packed (q|k|v, gate/up interleaved)
 
 
 def interleave_gate_up(gate, up):
@@ -95,6 +96,16 @@ def rope_tables(cfg, max_pos, device):
 
 
 KV_CACHE_DTYPES = {None: "float32", "auto": "float32", "float32": "float32", "fp16": "float16", "float16": "float16", "half": "float16"}
+
+
+def _eos_set(eos_token_id):
+    """eos_token_id: one id, a list / tuple / set of ids, or None -> set of ids"""
+    return set(eos_token_id if isinstance(eos_token_id, (list, tuple, set)) else ([] if eos_token_id is None else [eos_token_id]))
+
+
+def _eos_end(toks, eos):
+    """length of toks up to and including its first EOS token; None without one"""
+    return next((i + 1 for i, t in enumerate(toks) if t in eos), None)
 
 
 def kv_cache_dtype_name(kv_cache_dtype):
@@ -349,17 +360,34 @@ class ChatTSForCausalLM:
 
     def _finalize(self):
         """Allocate activations / KV cache and create the C-side decoder handle (borrowing all pointers)."""
-        cfg, plan, dev, lib = self.config, self.plan, self.device, self.lib
-        T = self._tensors
-        H, d = cfg.hidden_size, cfg.head_dim
+        cfg, plan = self.config, self.plan
         max_pos = max(self.max_ctx, 64)
-        T["cos"], T["sin"] = rope_tables(cfg, max_pos, dev)
+        self._tensors["cos"], self._tensors["sin"] = rope_tables(cfg, max_pos, self.device)
+        self._quantize_projections()
+        # decode attention: one wave per 16-key tile; slots beyond the live context exit immediately
+        self.n_splits = max(1, min(64, (self.max_ctx + 15) // 16))
+        dc = _lib.DecoderConfig(hidden=cfg.hidden_size, n_layers=cfg.num_hidden_layers, n_q=plan.nq, n_kv=plan.nkv, head_dim=cfg.head_dim,
+                                inter=plan.inter, vocab_local=plan.vocab, vocab_offset=plan.v0,
+                                rms_eps=cfg.rms_norm_eps, max_ctx=self.max_ctx, max_pos=max_pos, tp_world=plan.world,
+                                embed_rows=cfg.vocab_size, embed_offset=0,       # the embedding table is replicated
+                                w8_format=_lib.W8_INT8 if self.weight_format == "int8" else _lib.W8_FP8)
+        ws_bytes = self._workspace_bytes(dc)
+        self._alloc_buffers(ws_bytes)
+        self._tiled = self._tiled_copies()
+        self._f16q = self._f16q_copies()
+        self._layer_arr = self._layer_weights()
+        self._create_decoder(dc, ws_bytes)
+        if plan.world > 1 and self.use_p2p and getattr(self.comm, "dist", None) is not None and self._tp is None:
+            self._attach_p2p()
+
+    def _quantize_projections(self):
+        T = self._tensors
         if self.weight_format in ("fp8", "int8") and "lm_head8" not in T:
             # quantise every decoder projection once; the bf16 tensors are REPLACED by the (bf16-exact) dequantised
             # values so prefill (bf16 MFMA GEMM), batched decode and the 8-bit decode GEMV all see the same weights
             quant = quantize_fp8_rows if self.weight_format == "fp8" else quantize_int8_rows
             for lw in self.layers:
-                for name in ("qkv", "o", "gate_up", "down"):
+                for name in PROJECTIONS:
                     lw[name + "8"], lw[name + "8_scale"], lw[name] = quant(lw[name])
             tied = T["lm_head"].data_ptr() == T["embed"].data_ptr()
             T["lm_head8"], T["lm_head8_scale"], deq = quant(T["lm_head"])
@@ -369,16 +397,12 @@ class ChatTSForCausalLM:
         if self.weight_format == "int4" and self.layers and "qkv4" not in self.layers[0]:
             # round-to-nearest 4-bit codes of every decoder projection; the bf16 tensors are REPLACED by the dequantised values
             for lw in self.layers:
-                for name in ("qkv", "o", "gate_up", "down"):
+                for name in PROJECTIONS:
                     q, sc, z, lw[name] = quantize_int4_rows(lw[name], self.int4_group)
                     lw[name + "4"], lw[name + "4_sz"] = pack_int4(q, sc, z)
-        # decode attention: one wave per 16-key tile; slots beyond the live context exit immediately
-        self.n_splits = max(1, min(64, (self.max_ctx + 15) // 16))
-        dc = _lib.DecoderConfig(hidden=H, n_layers=cfg.num_hidden_layers, n_q=plan.nq, n_kv=plan.nkv, head_dim=d,
-                                inter=plan.inter, vocab_local=plan.vocab, vocab_offset=plan.v0,
-                                rms_eps=cfg.rms_norm_eps, max_ctx=self.max_ctx, max_pos=max_pos, tp_world=plan.world,
-                                embed_rows=cfg.vocab_size, embed_offset=0,       # the embedding table is replicated
-                                w8_format=_lib.W8_INT8 if self.weight_format == "int8" else _lib.W8_FP8)
+
+    def _workspace_bytes(self, dc):
+        lib, plan, H = self.lib, self.plan, self.config.hidden_size
         ws_bytes = int(lib.chatts_decoder_workspace(C.byref(dc), self.t_max, self.n_splits))
         ws_bytes = max(ws_bytes, int(lib.chatts_linear_workspace(self.t_max, plan.vocab, H)))
         for m in range(2, self.max_batch + 1):     # batched lm_head
@@ -388,7 +412,11 @@ class ChatTSForCausalLM:
         # the prefill attention's K / V planes (kv_planes_kernel: 32 KB per (kv head, 32-key tile)) for a sequence of max_ctx positions:
         # with the workspace sized for them the planes kernel is taken at EVERY chunk position, so the same prompt never changes
         # kernel (and summation order) with where a chunk starts
-        ws_bytes = max(ws_bytes, ((self.max_ctx + 31) // 32) * plan.nkv * 4 * 32 * d * 2 + 256)
+        return max(ws_bytes, ((self.max_ctx + 31) // 32) * plan.nkv * 4 * 32 * self.config.head_dim * 2 + 256)
+
+    def _alloc_buffers(self, ws_bytes):
+        cfg, plan, dev = self.config, self.plan, self.device
+        H, d = cfg.hidden_size, cfg.head_dim
         MB = self.max_batch
         f32 = dict(dtype=torch.float32, device=dev)
         qkv_n = (plan.nq + 2 * plan.nkv) * d
@@ -436,32 +464,40 @@ class ChatTSForCausalLM:
                 self._kv.reserve(sl, self.max_ctx)
                 self._kv.retire(sl)
                 self._push_kv_row(sl)
-        self._tiled = []
-        tile_ok = self.prefill_tiled_weights
+
+    def _tiled_copies(self):
+        """per layer {projection: copy in the prefill kernel's tiled layout} (prefill_tiled_weights)"""
+        lib, dev = self.lib, self.device
+        out, tile_ok = [], self.prefill_tiled_weights
         for lw in self.layers:
             tiled = {}
             if tile_ok:
                 # the copies are an optimisation: never let them take the memory the KV cache / activations of a large configuration need
-                need = sum(lw[n].numel() * 2 for n in ("qkv", "o", "gate_up", "down"))
+                need = sum(lw[n].numel() * 2 for n in PROJECTIONS)
                 free = torch.cuda.mem_get_info(dev)[0]
                 if free < need + (8 << 30):
                     import warnings
-                    warnings.warn(f"prefill_tiled_weights: {free / 2**30:.1f} GiB free - layers {len(self._tiled)}.. keep the row-major weights only")
+                    warnings.warn(f"prefill_tiled_weights: {free / 2**30:.1f} GiB free - layers {len(out)}.. keep the row-major weights only")
                     tile_ok = False
             if tile_ok:
-                for name in ("qkv", "o", "gate_up", "down"):
+                for name in PROJECTIONS:
                     w = lw[name]
                     rows, k = w.shape
                     if k % 64 == 0 and w.is_contiguous():
-                        out = torch.empty(int(lib.chatts_tile_bf16_elems(rows, k)), dtype=torch.bfloat16, device=dev)
-                        _lib.check(lib.chatts_tile_bf16(w.data_ptr(), rows, k, k, out.data_ptr(), _lib.stream_ptr()))
-                        tiled[name] = out
-            self._tiled.append(tiled)
-        self._f16q = []
+                        t = torch.empty(int(lib.chatts_tile_bf16_elems(rows, k)), dtype=torch.bfloat16, device=dev)
+                        _lib.check(lib.chatts_tile_bf16(w.data_ptr(), rows, k, k, t.data_ptr(), _lib.stream_ptr()))
+                        tiled[name] = t
+            out.append(tiled)
+        return out
+
+    def _f16q_copies(self):
+        """per layer {projection: (w16, w8, w8e)} of precision='f16q' (empty dicts otherwise)"""
+        lib, dev = self.lib, self.device
+        out = []
         for lw in self.layers:
             qd = {}
             if self.precision == "f16q":
-                for name in ("qkv", "o", "gate_up", "down"):
+                for name in PROJECTIONS:
                     w = lw[name]
                     rows, k = w.shape
                     if k % 128 or not w.is_contiguous():
@@ -476,29 +512,25 @@ class ChatTSForCausalLM:
                     _lib.check(lib.chatts_tile_bf16(w16.data_ptr(), rows, k, k, w16t.data_ptr(), _lib.stream_ptr()))
                     _lib.check(lib.chatts_tile_e4m3(w8.data_ptr(), rows, k, k, w8t.data_ptr(), _lib.stream_ptr()))
                     qd[name] = (w16t, w8t, w8e)
-            self._f16q.append(qd)
-        arr = (_lib.LayerWeights * L)()
+            out.append(qd)
+        return out
+
+    def _layer_weights(self):
+        """the C side's per-layer pointer array: every weight format and copy present (NULL for the absent ones)"""
+        arr = (_lib.LayerWeights * self.config.num_hidden_layers)()
         for i, lw in enumerate(self.layers):
-            tl = self._tiled[i]
-            fq = {f"{n}{suf}": _lib.ptr(t3[j]) for n, t3 in self._f16q[i].items() for j, suf in enumerate(("16", "_q8", "_q8e"))}
-            arr[i] = _lib.LayerWeights(**fq, qkv_t=_lib.ptr(tl.get("qkv")), o_t=_lib.ptr(tl.get("o")), gate_up_t=_lib.ptr(tl.get("gate_up")),
-                                       down_t=_lib.ptr(tl.get("down")),
-                                       input_norm=_lib.ptr(lw["input_norm"]), qkv=_lib.ptr(lw["qkv"]),
-                                       qkv_bias=_lib.ptr(lw.get("qkv_bias")), q_norm=_lib.ptr(lw.get("q_norm")),
-                                       k_norm=_lib.ptr(lw.get("k_norm")), o=_lib.ptr(lw["o"]),
-                                       post_norm=_lib.ptr(lw["post_norm"]), gate_up=_lib.ptr(lw["gate_up"]),
-                                       down=_lib.ptr(lw["down"]),
-                                       qkv8=_lib.ptr(lw.get("qkv8")), qkv8_scale=_lib.ptr(lw.get("qkv8_scale")),
-                                       o8=_lib.ptr(lw.get("o8")), o8_scale=_lib.ptr(lw.get("o8_scale")),
-                                       gate_up8=_lib.ptr(lw.get("gate_up8")), gate_up8_scale=_lib.ptr(lw.get("gate_up8_scale")),
-                                       down8=_lib.ptr(lw.get("down8")), down8_scale=_lib.ptr(lw.get("down8_scale")),
-                                       qkv4=_lib.ptr(lw.get("qkv4")), qkv4_sz=_lib.ptr(lw.get("qkv4_sz")),
-                                       o4=_lib.ptr(lw.get("o4")), o4_sz=_lib.ptr(lw.get("o4_sz")),
-                                       gate_up4=_lib.ptr(lw.get("gate_up4")), gate_up4_sz=_lib.ptr(lw.get("gate_up4_sz")),
-                                       down4=_lib.ptr(lw.get("down4")), down4_sz=_lib.ptr(lw.get("down4_sz")),
-                                       w4_group=self.int4_group)
-        self._layer_arr = arr
-        dw = _lib.DecoderWeights(layers=arr, final_norm=_lib.ptr(T["final_norm"]), lm_head=_lib.ptr(T["lm_head"]),
+            tl, fq = self._tiled[i], self._f16q[i]
+            ts = {n: lw.get(n) for n in ("input_norm", "qkv_bias", "q_norm", "k_norm", "post_norm")}
+            for n in PROJECTIONS:
+                ts.update({n: lw[n], n + "_t": tl.get(n)})
+                ts.update({n + suf: lw.get(n + suf) for suf in ("8", "8_scale", "4", "4_sz")})
+                ts.update(zip((n + "16", n + "_q8", n + "_q8e"), fq.get(n, (None, None, None))))
+            arr[i] = _lib.LayerWeights(**{k: _lib.ptr(t) for k, t in ts.items()}, w4_group=self.int4_group)
+        return arr
+
+    def _create_decoder(self, dc, ws_bytes):
+        lib, T, B = self.lib, self._tensors, self.buf
+        dw = _lib.DecoderWeights(layers=self._layer_arr, final_norm=_lib.ptr(T["final_norm"]), lm_head=_lib.ptr(T["lm_head"]),
                                  lm_head8=_lib.ptr(T.get("lm_head8")), lm_head8_scale=_lib.ptr(T.get("lm_head8_scale")),
                                  embed=_lib.ptr(T["embed"]), cos_tab=_lib.ptr(T["cos"]), sin_tab=_lib.ptr(T["sin"]))
         db = _lib.DecoderBuffers(kv_k=_lib.ptr(B["kv_k"]), kv_v=_lib.ptr(B["kv_v"]), x=_lib.ptr(B["x"]),
@@ -517,35 +549,37 @@ class ChatTSForCausalLM:
         if not h:
             raise _lib.ChattsError(-1, lib.chatts_last_error().decode())
         self._decoder = C.c_void_p(h)
-        self._graph = None
-        self._graph_batched = None
+        self._drop_graphs()
         if self.precision == "fp8":              # speed mode: prefill chunks and the TS encoder on the fp8 matrix pipe
             _lib.check(lib.chatts_decoder_set_prefill_fp8(self._decoder, 1))
             self.ts_encoder.set_precision("fp8")
         if self.precision == "f16q":             # parity-grade prefill on the f16 + fp8 matrix pipes (the TS encoder keeps bf16x2)
             _lib.check(lib.chatts_decoder_set_prefill_f16q(self._decoder, 1))
-        if plan.world > 1 and self.use_p2p and getattr(self.comm, "dist", None) is not None and self._tp is None:
-            from .tp import P2PExchange
-            ex, err = None, None
-            try:
-                ex = P2PExchange.create(self.comm, self.exchange_elems(), self.exchange_bulk_elems())
-            except Exception as e:               # e.g. no IPC mapping between these two devices
-                err = e
-            # every rank must take the same path: agree before anyone attaches
-            oks = [None] * plan.world
-            self.comm.dist.all_gather_object(oks, err is None, group=self.comm.group)
-            if all(oks):
-                self.attach_exchange(ex)
-            else:
-                if ex is not None:
-                    ex.close()
-                if self.max_batch > 1:
-                    raise RuntimeError(f"the peer-to-peer exchange could not be set up on ranks {[r for r, ok in enumerate(oks) if not ok]} "
-                                       f"({err}); batched decode under tensor parallelism needs it")
-                import warnings
-                warnings.warn(f"peer-to-peer exchange unavailable on ranks {[r for r, ok in enumerate(oks) if not ok]} ({err}): "
-                              "decode-sized sums go through RCCL from the host (slower, no hipGraph)")
-                self.use_p2p = False
+
+    def _attach_p2p(self):
+        """TP: set up the peer-to-peer exchange on every rank, or on none (then batch-1 decode falls back to host-driven RCCL)"""
+        from .tp import P2PExchange
+        world = self.plan.world
+        ex, err = None, None
+        try:
+            ex = P2PExchange.create(self.comm, self.exchange_elems(), self.exchange_bulk_elems())
+        except Exception as e:               # e.g. no IPC mapping between these two devices
+            err = e
+        # every rank must take the same path: agree before anyone attaches
+        oks = [None] * world
+        self.comm.dist.all_gather_object(oks, err is None, group=self.comm.group)
+        if all(oks):
+            self.attach_exchange(ex)
+        else:
+            if ex is not None:
+                ex.close()
+            if self.max_batch > 1:
+                raise RuntimeError(f"the peer-to-peer exchange could not be set up on ranks {[r for r, ok in enumerate(oks) if not ok]} "
+                                   f"({err}); batched decode under tensor parallelism needs it")
+            import warnings
+            warnings.warn(f"peer-to-peer exchange unavailable on ranks {[r for r, ok in enumerate(oks) if not ok]} ({err}): "
+                          "decode-sized sums go through RCCL from the host (slower, no hipGraph)")
+            self.use_p2p = False
 
     def exchange_bulk_elems(self):
         """float32 elements of the largest prefill-sized sum: one chunk of partial [t_max, H] rows (chatts_allreduce_bulk)"""
@@ -559,8 +593,7 @@ class ChatTSForCausalLM:
         """Bind this rank's P2PExchange (chatts_amd/tp.py): the whole TP decode step then runs behind one C call / one hipGraph."""
         _lib.check(self.lib.chatts_decoder_set_tp(self._decoder, exchange.handle if exchange is not None else None))
         self._tp = exchange
-        self._graph = None
-        self._graph_batched = None
+        self._drop_graphs()
 
     def __del__(self):
         try:
@@ -605,8 +638,7 @@ class ChatTSForCausalLM:
         ts = self._parse_and_validate_ts_input(timeseries)
         feats, patch_cnt = self.ts_encoder(ts, valid_lengths=valid_lengths)
         if valid_lengths is not None:
-            ps = self.ts_encoder.patch_size
-            counts = [(int(v) + ps - 1) // ps for v in valid_lengths]
+            counts = self._patch_counts(valid_lengths)
         else:
             counts = patch_cnt.tolist()
         out, s = [], 0
@@ -747,9 +779,9 @@ class ChatTSForCausalLM:
         keep = set(protect)
         first = int(write_from) // self._kv.block_size
         if idents is not None and self.enable_prefix_caching:
-            n, src = self._match_prefix(slot, idents)
+            n, src = prefix_cache.match_prefix(self._slot_idents, idents, slot)
             n = min(n, len(idents) - 1)
-            if src >= 0 and n >= 16:
+            if src >= 0 and n >= prefix_cache.MIN_REUSE:
                 keep.add(src)
                 first = n // self._kv.block_size          # own slot: rows below stay; other slot: blocks below get adopted
         order = sorted(range(self.max_batch), key=lambda sl: len(self._slot_idents[sl]))       # least resident first
@@ -764,11 +796,9 @@ class ChatTSForCausalLM:
 
     def request_tokens(self, ids, series=None, lengths=None):
         """expanded prompt length of a request (host arithmetic when the series lengths are known)"""
-        ps = self.config.ts["patch_size"]
         if series is not None and series.shape[0] > 0 and lengths is None:
             lengths = self.ts_encoder.get_patch_cnt(series.to(self.device, dtype=torch.float32))[0].tolist()
-        counts = [(int(v) + ps - 1) // ps for v in (lengths or [])]
-        return len(self.expand_input_ids(list(ids), counts))
+        return len(self.expand_input_ids(list(ids), self._patch_counts(lengths or [])))
 
     def kv_stats(self):
         if self._kv is None:
@@ -817,8 +847,7 @@ class ChatTSForCausalLM:
             return
         _lib.check(self.lib.chatts_decoder_set_sampling(self._decoder, None if args is None else C.byref(args)))
         self._sampling, self._sampling_key = args, key
-        self._graph = None               # the captured steps have the old selection kernel baked in
-        self._graph_batched = None
+        self._drop_graphs()              # the captured steps have the old selection kernel baked in
 
     def _sampling_arrays(self):
         if "samp_temp" not in self.buf:
@@ -844,8 +873,7 @@ class ChatTSForCausalLM:
         args = self._rows_args(0)
         _lib.check(self.lib.chatts_decoder_set_sampling(self._decoder, C.byref(args)))
         self._sampling, self._sampling_key = args, "rows"
-        self._graph = None
-        self._graph_batched = None
+        self._drop_graphs()
 
     def set_slot_sampling(self, slot, temperature=0.0, top_k=0, top_p=1.0, seed=0):
         """Sampling settings of the sequence in cache slot `slot`: used by every step in per-slot mode (set_sampling_rows), inert in
@@ -874,8 +902,7 @@ class ChatTSForCausalLM:
         if on:
             self._logprob_rings()
         self._logprobs_on = on
-        self._graph = None
-        self._graph_batched = None
+        self._drop_graphs()
 
     def _logprob_rings(self):
         if "lp" not in self.buf:
@@ -918,13 +945,10 @@ class ChatTSForCausalLM:
     def _select_token(self):
         """logits of this rank -> next token in B['token'] (appended to out_tokens, step bumped) on every rank: greedy or the
         configured sampler, agreed across TP ranks by chatts_decoder_select_tokens ((max, idx) pairs / gathered logits)."""
-        lib, st, B = self.lib, _lib.stream_ptr(), self.buf
         if self.plan.world == 1 or self._tp is not None:
-            _lib.check(lib.chatts_decoder_select_tokens(self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, _lib.ptr(B["token"]),
-                                                        _lib.ptr(B["token_logit"]), _lib.ptr(B["out_tokens"]), 0,
-                                                        _lib.ptr(B["step"]), None, 0, None, st))
-            self._logprobs_after(B["logits"], 1, 0)
+            self._select_one(0, 0, None)
             return
+        lib, st, B = self.lib, _lib.stream_ptr(), self.buf
         self._select_token_host_tp()
         if self._logprobs_on:     # every rank: the same kernel on the same gathered logits
             full = self.comm.all_gather_cat(B["logits"])
@@ -933,6 +957,16 @@ class ChatTSForCausalLM:
                                                    _lib.ptr(B["token"]), _lib.ptr(B["step"]), R["stride"], _lib.ptr(R["lp"]),
                                                    _lib.ptr(R["rank"]), _lib.ptr(R["top_ids"]), _lib.ptr(R["top_lp"]),
                                                    _lib.ptr(B["ws"]), B["ws"].numel(), st))
+
+    def _select_one(self, slot, out_stride, sampling):
+        """chatts_decoder_select_tokens on the logits of one row -> the sequence in cache slot `slot` (+ its logprobs).
+        sampling: SamplingArgs for this call, None = the decoder's own setting."""
+        B = self.buf
+        _lib.check(self.lib.chatts_decoder_select_tokens(
+            self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
+            B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), out_stride,
+            B["step_all"][slot:].data_ptr(), None, 0, None if sampling is None else C.byref(sampling), _lib.stream_ptr()))
+        self._logprobs_after(B["logits"], 1, slot)
 
     def _select_token_host_tp(self):
         lib, st, B = self.lib, _lib.stream_ptr(), self.buf
@@ -992,25 +1026,34 @@ class ChatTSForCausalLM:
     def _capture(self, warm=True):
         """Capture one decode step.  warm: run one eager step first (populates every lazy host-side cache; under tensor
         parallelism all ranks do, so it really exchanges) and restore the state; capturing itself executes nothing."""
+        self._graph = self._capture_graph(self._decode_step_eager, ("pos", "step", "token", "token_logit", "x", "out_tokens"), warm)
+
+    def _capture_graph(self, step_fn, keys, warm=True):
+        """-> a graph of step_fn(); the buffers `keys` (the decode-loop state step_fn advances) are left as they were."""
         B = self.buf
-        saved = {k: B[k].clone() for k in ("pos", "step", "token", "token_logit", "x", "out_tokens")}
+        saved = {k: B[k].clone() for k in keys}
         torch.cuda.synchronize()
         if warm:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                self._decode_step_eager()
+                step_fn()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             for k, v in saved.items():
                 B[k].copy_(v)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_step_eager()
+            step_fn()
         torch.cuda.synchronize()
         for k, v in saved.items():          # capture does not execute, but keep the state pristine anyway
             B[k].copy_(v)
-        self._graph = g
+        return g
+
+    def _drop_graphs(self):
+        """forget the captured decode steps: the next one captures again (after a change of what a step launches)"""
+        self._graph = None
+        self._graph_batched = None
 
     # ---------------------------------------------------------------------------------------------
     # batched decode / continuous batching (SURVEY.md section 8f item 1; TP = 1)
@@ -1046,79 +1089,47 @@ class ChatTSForCausalLM:
         if not self.use_graph:
             return self._batched_step_eager()
         if self._graph_batched is None:
-            B = self.buf
-            keys = ("pos_all", "step_all", "token_all", "token_logit_all", "out_tokens_all")
-            saved = {k: B[k].clone() for k in keys}
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._batched_step_eager()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            for k in keys:
-                B[k].copy_(saved[k])
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._batched_step_eager()
-            torch.cuda.synchronize()
-            for k in keys:
-                B[k].copy_(saved[k])
-            self._graph_batched = g
+            self._graph_batched = self._capture_graph(
+                self._batched_step_eager, ("pos_all", "step_all", "token_all", "token_logit_all", "out_tokens_all"))
         self._graph_batched.replay()
 
-    # ---- prefix reuse ---------------------------------------------------------------------------------
-    @staticmethod
-    def _token_idents(full, series, lengths, counts, ts0):
-        """Identity of every token of an EXPANDED prompt: the id for text tokens; for a <ts> placeholder the digest of its
-        series' (value, mask) row + the patch index - two placeholder rows hold the same embedding iff those agree."""
-        import hashlib
-        digests = []
-        if series is not None and len(counts):
-            host = series.detach().cpu().numpy() if hasattr(series, "detach") else np.asarray(series)
-            for i, L in enumerate(lengths):
-                digests.append(hashlib.blake2b(np.ascontiguousarray(host[i].reshape(-1)[:2 * int(L)]).tobytes(), digest_size=8).digest())
-        out, k, j = [], -1, 0
-        owner = []                                   # series index of every placeholder, in order
-        for i, c in enumerate(counts):
-            owner += [(i, p) for p in range(int(c))]
-        for t in full:
-            if t == ts0:
-                i, pidx = owner[j]
-                j += 1
-                out.append((digests[i], pidx))
-            else:
-                out.append(t)
-        return out
+    # ---- prefix reuse (policy: chatts_amd/prefix_cache.py) and request preparation ---------------------------------------
+    def _patch_counts(self, lengths):
+        """valid series lengths -> TS encoder patches (<ts> placeholders) per series"""
+        ps = self.config.ts["patch_size"]
+        return [(int(v) + ps - 1) // ps for v in lengths]
 
     def _request_idents(self, ids, series, lengths):
         """token identities of a request before it is admitted (slot choice): host-side only, no device work"""
         if not self.enable_prefix_caching:
             return None
-        ps = self.config.ts["patch_size"]
         if series is not None and series.shape[0] > 0 and lengths is None:
             return None
-        counts = [(int(v) + ps - 1) // ps for v in (lengths or [])]
+        counts = self._patch_counts(lengths or [])
         try:
             full = self.expand_input_ids(list(ids), counts)
         except ValueError:
             return None
-        return self._token_idents(full, series, lengths, counts, self.config.ts_token_start_index)
+        return prefix_cache.token_idents(full, series, lengths, counts, self.config.ts_token_start_index)
 
-    def _match_prefix(self, slot, idents, exclude=()):
-        """(n, src): the longest prefix of `idents` resident in some cache slot (ties prefer `slot` itself: zero copy)."""
-        best, src = 0, -1
-        for s, have in enumerate(self._slot_idents):
-            if s in exclude:
-                continue
-            n = 0
-            for a, b in zip(idents, have):
-                if a != b:
-                    break
-                n += 1
-            if n > best or (n == best and s == slot and n > 0):
-                best, src = n, s
-        return best, src
+    def _prepare_request(self, ids, series, lengths, max_new_tokens):
+        """TS encoder, prompt expansion, embeddings and token identities of one request - what every admission path does before it
+        touches a cache slot.  -> (T, emb [T, H], idents, series on the device, lengths) (series / lengths resolved: None lengths
+        are measured on the device)."""
+        mm, counts = None, []
+        if series is not None and series.shape[0] > 0:
+            series = series.to(self.device, dtype=torch.float32)
+            if lengths is None:
+                lengths = self.ts_encoder.get_patch_cnt(series)[0].tolist()
+            counts = self._patch_counts(lengths)
+            mm = self.get_multimodal_embeddings(timeseries=series, valid_lengths=lengths)
+        full = self.expand_input_ids(list(ids), counts)
+        T = len(full)
+        if T + max_new_tokens > self.max_ctx:       # a sequence must never outgrow its cache
+            raise ValueError(f"prompt ({T}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
+        emb = self.get_input_embeddings(torch.tensor(full, dtype=torch.int64), mm)
+        idents = prefix_cache.token_idents(full, series, lengths, counts, self.config.ts_token_start_index)
+        return T, emb, idents, series, lengths
 
     def _reuse_prefix(self, slot, idents, T, exclude=()):
         """Longest prefix of `idents` already resident in some slot's cache -> copy those K/V rows into `slot` (nothing to copy
@@ -1128,9 +1139,9 @@ class ChatTSForCausalLM:
         replaced = self._kv_replaced.pop(slot, set())      # (paged) blocks reserve_kv swapped for private, EMPTY ones
         if not self.enable_prefix_caching:
             return 0
-        best, src = self._match_prefix(slot, idents, exclude)
+        best, src = prefix_cache.match_prefix(self._slot_idents, idents, slot, exclude)
         n = min(best, T - 1)
-        if n < 16:                                   # not worth a copy + a ragged prefill start
+        if n < prefix_cache.MIN_REUSE:
             return 0
         if self._kv is not None:
             # paged: nothing is copied.  Another slot's prefix is SHARED block by block (reference counted), so the reuse ends at a
@@ -1147,7 +1158,7 @@ class ChatTSForCausalLM:
                 lost = [i for i in replaced if i * bs < n]
                 if lost:
                     n = min(lost) * bs
-                if n < 16:
+                if n < prefix_cache.MIN_REUSE:
                     return 0
         elif src != slot:
             B = self.buf
@@ -1170,36 +1181,12 @@ class ChatTSForCausalLM:
         one whose resident tokens are least worth keeping (fewest)."""
         if not self.enable_prefix_caching or idents is None:
             return free_slots[0]
-        def match(s):
-            n = 0
-            for a, b in zip(idents, self._slot_idents[s]):
-                if a != b:
-                    break
-                n += 1
-            return n
-        best = max(free_slots, key=match)
-        if match(best) >= 16:
-            return best
-        return min(free_slots, key=lambda s: len(self._slot_idents[s]))
+        return prefix_cache.pick_slot(self._slot_idents, free_slots, idents)
 
     def admit_begin(self, slot, ids, series, lengths, max_new_tokens=1):
         """First half of an admission into cache slot `slot`: TS encoder, prompt expansion, embeddings, KV reservation and prefix
         reuse - everything but the prefill itself.  -> the state admit_step() consumes."""
-        cfg = self.config
-        ps = cfg.ts["patch_size"]
-        mm, counts = None, []
-        if series is not None and series.shape[0] > 0:
-            series = series.to(self.device, dtype=torch.float32)
-            if lengths is None:
-                lengths = self.ts_encoder.get_patch_cnt(series)[0].tolist()
-            counts = [(int(v) + ps - 1) // ps for v in lengths]
-            mm = self.get_multimodal_embeddings(timeseries=series, valid_lengths=lengths)
-        full = self.expand_input_ids(list(ids), counts)
-        T = len(full)
-        if T + max_new_tokens > self.max_ctx:       # same bound as generate_one: a sequence must never outgrow its cache
-            raise ValueError(f"prompt ({T}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
-        emb = self.get_input_embeddings(torch.tensor(full, dtype=torch.int64), mm)
-        idents = self._token_idents(full, series, lengths, counts, cfg.ts_token_start_index)
+        T, emb, idents, _, _ = self._prepare_request(ids, series, lengths, max_new_tokens)
         self.reserve_kv(slot, T + max_new_tokens, idents)
         n0 = self._reuse_prefix(slot, idents, T)
         self._slot_idents[slot] = []                # not a prefix source for others until all of its rows exist
@@ -1243,11 +1230,7 @@ class ChatTSForCausalLM:
         elif sa is not None:   # the batched steps draw with (seed, slot, step); this single-row call would see slot 0: fold the slot into the seed
             sa1 = _lib.SamplingArgs(temperature=sa.temperature, top_k=sa.top_k, top_p=sa.top_p,
                                     seed=(sa.seed ^ (0x51ED27 * (slot + 1))) & 0xFFFFFFFF, n_kept=None, kept_mass=None)
-        _lib.check(self.lib.chatts_decoder_select_tokens(
-            self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
-            B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), B["out_tokens_all"].shape[1],
-            B["step_all"][slot:].data_ptr(), None, 0, None if sa1 is None else C.byref(sa1), st))
-        self._logprobs_after(B["logits"], 1, slot)
+        self._select_one(slot, B["out_tokens_all"].shape[1], sa1)
 
     def plan_pack(self, candidates, free_slots):
         """Which of the waiting requests should be prefilled TOGETHER (chatts_decoder_prefill_packed).  candidates: list of
@@ -1256,37 +1239,24 @@ class ChatTSForCausalLM:
         next round (it will then reuse that request's K/V rows instead of computing them again).  -> indices into candidates."""
         if self.plan.world != 1 or len(free_slots) < 2 or len(candidates) < 2:
             return []
-        ps = self.config.ts["patch_size"]
         pack, rows, pack_idents = [], 0, []
         for i, (ids, series, lengths, max_new) in enumerate(candidates):
             if len(pack) >= len(free_slots):
                 break
             idents = self._request_idents(ids, series, lengths)
             if idents is None:          # lengths unknown / prefix caching off: size by the expanded prompt alone
-                counts = [(int(v) + ps - 1) // ps for v in (lengths or [])]
                 try:
-                    T = len(self.expand_input_ids(list(ids), counts))
+                    T = len(self.expand_input_ids(list(ids), self._patch_counts(lengths or [])))
                 except ValueError:
                     continue
-                need, idents = T, None
+                need = T
             else:
                 T = len(idents)
-                n, _ = self._match_prefix(-1, idents)
+                n, _ = prefix_cache.match_prefix(self._slot_idents, idents, -1)
                 n = min(n, T - 1)
-                need = T - (n if n >= 16 else 0)
-                dup = False
-                for other in pack_idents:
-                    if other is None:
-                        continue
-                    k = 0
-                    for a, b in zip(idents, other):
-                        if a != b:
-                            break
-                        k += 1
-                    if k >= max(16, T // 2):
-                        dup = True
-                        break
-                if dup:
+                need = T - (n if n >= prefix_cache.MIN_REUSE else 0)
+                if any(other is not None and prefix_cache.common_prefix_len(idents, other) >= max(prefix_cache.MIN_REUSE, T // 2)
+                       for other in pack_idents):
                     continue
             if T + max_new > self.max_ctx or rows + need > self.t_max:
                 continue
@@ -1298,8 +1268,7 @@ class ChatTSForCausalLM:
     def _admit_packed(self, items):
         """Prefill several requests in ONE packed pass.  items: list of (slot, ids, series, lengths, max_new_tokens) with distinct
         free slots whose uncached rows fit max_prefill_tokens together (plan_pack).  Returns the prompt lengths."""
-        cfg, B = self.config, self.buf
-        ps = cfg.ts["patch_size"]
+        B = self.buf
         segs, embs, Ts, row, late = [], [], [], 0, []
         if self._kv_dynamic:        # oversubscribed block pool: reserve for EVERY member before anything changes, or for none
             from .kv_blocks import KvPoolExhausted
@@ -1321,19 +1290,7 @@ class ChatTSForCausalLM:
                     self._kv.retire(sl)
                 raise
         for slot, ids, series, lengths, max_new in items:
-            mm, counts = None, []
-            if series is not None and series.shape[0] > 0:
-                series = series.to(self.device, dtype=torch.float32)
-                if lengths is None:
-                    lengths = self.ts_encoder.get_patch_cnt(series)[0].tolist()
-                counts = [(int(v) + ps - 1) // ps for v in lengths]
-                mm = self.get_multimodal_embeddings(timeseries=series, valid_lengths=lengths)
-            full = self.expand_input_ids(list(ids), counts)
-            T = len(full)
-            if T + max_new > self.max_ctx:
-                raise ValueError(f"prompt ({T}) + max_new_tokens ({max_new}) exceeds max_ctx={self.max_ctx}")
-            emb = self.get_input_embeddings(torch.tensor(full, dtype=torch.int64), mm)
-            idents = self._token_idents(full, series, lengths, counts, cfg.ts_token_start_index)
+            T, emb, idents, series, lengths = self._prepare_request(ids, series, lengths, max_new)
             # reuse from ANY slot, the member's own and other members' included: every K/V row copy is enqueued here, i.e. before
             # the packed pass overwrites anything; a slot stops being a source once its member has been processed (idents cleared)
             self.reserve_kv(slot, T + max_new, idents)       # (dynamic pool: already covered by the pre-pass above)
@@ -1383,8 +1340,7 @@ class ChatTSForCausalLM:
             if logprobs is None:
                 return outs
             return [o[0] if k is not None else o for o, k in zip(outs, ks)], [o[1] if k is not None else None for o, k in zip(outs, ks)]
-        eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple, set)) else
-                  ([] if eos_token_id is None else [eos_token_id]))
+        eos = _eos_set(eos_token_id)
         B = self.buf
         results = [None] * len(requests)
         entries = [None] * len(requests)
@@ -1396,13 +1352,12 @@ class ChatTSForCausalLM:
 
         def harvest(final=False):
             toks_all = B["out_tokens_all"].cpu()
-            if self._tp is not None and self._tp.status():
-                raise RuntimeError("tensor-parallel exchange timed out (a peer rank did not reach the collective): tokens are invalid")
+            self._check_exchange()
             for s, r in enumerate(slots):
                 if r is None:
                     continue
                 toks = toks_all[s, :produced[s]].tolist()
-                cut = next((i + 1 for i, t in enumerate(toks) if t in eos), None) if eos else None
+                cut = _eos_end(toks, eos)
                 if cut is not None or produced[s] >= max_new_tokens or final:
                     results[r] = toks[:cut] if cut is not None else toks[:max_new_tokens]
                     if ks[r] is not None:
@@ -1498,8 +1453,7 @@ class ChatTSForCausalLM:
             self.set_logprobs(True)
         self._prefill_request(ids, series, lengths, max_new_tokens)
         logits0 = self.buf["logits"].clone() if return_logits else None
-        eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple, set)) else
-                  ([] if eos_token_id is None else [eos_token_id]))
+        eos = _eos_set(eos_token_id)
         produced = 1
         toks = None
         while produced < max_new_tokens:
@@ -1510,16 +1464,16 @@ class ChatTSForCausalLM:
                 if any(t in eos for t in toks):
                     break
         toks = self.buf["out_tokens"][:produced].tolist()
-        if self._tp is not None and self._tp.status():
-            raise RuntimeError("tensor-parallel exchange timed out (a peer rank did not reach the collective): tokens are invalid")
-        if eos:
-            for i, t in enumerate(toks):
-                if t in eos:
-                    toks = toks[:i + 1]
-                    break
+        self._check_exchange()
+        toks = toks[:_eos_end(toks, eos)]
         self.note_generated(0, toks)
         out = (toks,) + ((logits0,) if return_logits else ()) + ((self.read_logprobs(0, 0, len(toks), logprobs),) if logprobs is not None else ())
         return out[0] if len(out) == 1 else out
+
+    def _check_exchange(self):
+        """TP: the tokens read since the last check are invalid if the peer-to-peer exchange timed out meanwhile"""
+        if self._tp is not None and self._tp.status():
+            raise RuntimeError("tensor-parallel exchange timed out (a peer rank did not reach the collective): tokens are invalid")
 
     def _check_logprobs(self, k):
         if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= self.max_logprobs:
@@ -1530,17 +1484,16 @@ class ChatTSForCausalLM:
         """Generator over the new tokens of ONE request: yields a list of token ids every `chunk` decode steps (chunk=1: token by
         token, what an SSE stream / HF TextStreamer consumes; each yield costs one device->host read of the tokens so far).
         Stops after an EOS token (which is yielded) or max_new_tokens.  Same kernels and tokens as generate_one."""
-        eos = set(eos_token_id if isinstance(eos_token_id, (list, tuple, set)) else ([] if eos_token_id is None else [eos_token_id]))
+        eos = _eos_set(eos_token_id)
         self._prefill_request(ids, series, lengths, max_new_tokens)
         produced, sent = 1, 0
         while True:
             if produced - sent >= chunk or produced >= max_new_tokens:
                 toks = self.buf["out_tokens"][sent:produced].tolist()
-                if self._tp is not None and self._tp.status():
-                    raise RuntimeError("tensor-parallel exchange timed out (a peer rank did not reach the collective): tokens are invalid")
-                hit = next((i for i, t in enumerate(toks) if t in eos), None)
-                if hit is not None:
-                    yield toks[:hit + 1]
+                self._check_exchange()
+                end = _eos_end(toks, eos)
+                if end is not None:
+                    yield toks[:end]
                     return
                 yield toks
                 sent = produced
@@ -1551,21 +1504,7 @@ class ChatTSForCausalLM:
 
     def _prefill_request(self, ids, series, lengths, max_new_tokens):
         """TS encode + merge + prefill + first token of one request on the single-sequence path -> prompt length T."""
-        cfg = self.config
-        ps = cfg.ts["patch_size"]
-        mm, counts = None, []
-        if series is not None and series.shape[0] > 0:
-            series = series.to(self.device, dtype=torch.float32)
-            if lengths is None:
-                lengths = self.ts_encoder.get_patch_cnt(series)[0].tolist()
-            counts = [(int(v) + ps - 1) // ps for v in lengths]
-            mm = self.get_multimodal_embeddings(timeseries=series, valid_lengths=lengths)
-        full = self.expand_input_ids(list(ids), counts)
-        T = len(full)
-        if T + max_new_tokens > self.max_ctx:
-            raise ValueError(f"prompt ({T}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
-        emb = self.get_input_embeddings(torch.tensor(full, dtype=torch.int64), mm)
-        idents = self._token_idents(full, series, lengths, counts, cfg.ts_token_start_index)
+        T, emb, idents, _, _ = self._prepare_request(ids, series, lengths, max_new_tokens)
         self.reserve_kv(0, T + max_new_tokens, idents)
         n0 = self._reuse_prefix(0, idents, T)
         self._slot_idents[0] = idents
