@@ -302,5 +302,8 @@ __device__ __forceinline__ void rope_kv_head(float a, float b, int h, int pos, i
 // host: validate the arguments of chatts_rope_kv_write and fill a RopeFuse (elementwise.hip)
 int rope_fuse_prepare(int t, int n_q, int n_kv, const float* q_norm_w, const float* k_norm_w, float norm_eps, const float* cos_tab,
                       const float* sin_tab, int pos0, const int32_t* pos0_dev, const ChattsKvCache* cache, RopeFuse* out);
+// host: chatts_rmsnorm_planes on rows ldx floats apart, arguments already validated (elementwise.hip; a projection's post-norm reads c at ldc)
+int launch_rmsnorm_planes(const float* x, int ldx, const float* w, uint16_t* hi, uint16_t* lo, int ldp, int t, int hidden, float eps,
+                          hipStream_t s);
 
 }  // namespace chatts

@@ -90,8 +90,8 @@ static int linear_impl(const ChattsLinearArgs* a, chatts_stream_t stream, const 
                    CHATTS_E_SHAPE, "linear: 4-bit weights need w4_sz, a power-of-two group size >= 16 that divides K, ldw4 >= K/2 and %% 8");
   if (a->post_norm_w)
     CHATTS_REQUIRE(a->m > 1 && a->c && a->post_hi && a->post_lo && a->ld_post >= a->n && a->ld_post % 4 == 0 && a->n % 4 == 0 &&
-                       (a->epilogue == CHATTS_EPI_NONE || a->epilogue == CHATTS_EPI_RESID) && !cplanes,
-                   CHATTS_E_BADARG, "linear: post-norm planes need M > 1, float32 c, EPI_NONE / EPI_RESID, both planes, ld_post >= N");
+                       a->ldc % 4 == 0 && (a->epilogue == CHATTS_EPI_NONE || a->epilogue == CHATTS_EPI_RESID) && !cplanes,
+                   CHATTS_E_BADARG, "linear: post-norm planes need M > 1, float32 c with ldc %% 4 == 0, EPI_NONE / EPI_RESID, both planes, ld_post >= N");
   if (a->tp_reduce) CHATTS_REQUIRE(a->m == 1, CHATTS_E_BADARG, "linear: tp_reduce is available for M == 1 (the decode GEMV) only");
   if (a->m == 1 && a->epilogue != CHATTS_EPI_GELU) return launch_gemv(a, as_stream(stream));
   CHATTS_REQUIRE(a->norm_w == nullptr, CHATTS_E_BADARG, "linear: fused RMSNorm is only available for M == 1");

@@ -7,12 +7,13 @@ namespace chatts {
 // ---- RMSNorm: one workgroup per row, float4 loads, wave-shuffle + LDS reduction --------------------
 // y = w * (x * rsqrt(mean(x^2) + eps))     (Qwen2RMSNorm.forward; same op order as the oracle)
 // PLANES: the row goes out as bf16 hi / lo planes (hi = bf16(y), lo = bf16(y - hi)), the LDS-DMA GEMM's operand format.
+// ldx: row stride of x (the public entry points: hidden; a projection's post-norm: its ldc).
 template <bool PLANES>
-__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
+__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                      float* __restrict__ y, int hidden, float eps,
                                                      uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, int ldp) {
   __shared__ float red[4];
-  const float* xr = x + (size_t)blockIdx.x * hidden;
+  const float* xr = x + (size_t)blockIdx.x * ldx;
   float* yr = PLANES ? nullptr : y + (size_t)blockIdx.x * hidden;
   float ss = 0.f;
   for (int k = threadIdx.x * 4; k < hidden; k += 1024) {
@@ -271,6 +272,14 @@ __global__ __launch_bounds__(256) void residual_add_kernel(float* __restrict__ x
   }
 }
 
+// chatts_rmsnorm_planes on rows ldx floats apart (arguments validated by the caller)
+int launch_rmsnorm_planes(const float* x, int ldx, const float* w, uint16_t* hi, uint16_t* lo, int ldp, int t, int hidden, float eps,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(rmsnorm_kernel<true>, dim3(t), dim3(256), 0, s, x, ldx, w, nullptr, hidden, eps, hi, lo, ldp);
+  CHATTS_CHECK_LAUNCH("rmsnorm_planes");
+  return CHATTS_OK;
+}
+
 }  // namespace chatts
 
 using namespace chatts;
@@ -281,7 +290,7 @@ extern "C" int chatts_rmsnorm(const float* x, const float* w, float* y, int t, i
   if (t == 0) return CHATTS_OK;
   CHATTS_REQUIRE(x && w && y, CHATTS_E_BADARG, "rmsnorm: null pointer");
   CHATTS_REQUIRE(hidden % 4 == 0, CHATTS_E_SHAPE, "rmsnorm: hidden %d not a multiple of 4", hidden);
-  hipLaunchKernelGGL(rmsnorm_kernel<false>, dim3(t), dim3(256), 0, as_stream(stream), x, w, y, hidden, eps, nullptr, nullptr, 0);
+  hipLaunchKernelGGL(rmsnorm_kernel<false>, dim3(t), dim3(256), 0, as_stream(stream), x, hidden, w, y, hidden, eps, nullptr, nullptr, 0);
   CHATTS_CHECK_LAUNCH("rmsnorm");
   return CHATTS_OK;
 }
@@ -293,10 +302,7 @@ extern "C" int chatts_rmsnorm_planes(const float* x, const float* w, chatts_bf16
   CHATTS_REQUIRE(x && w && hi && lo, CHATTS_E_BADARG, "rmsnorm_planes: null pointer");
   CHATTS_REQUIRE(hidden % 4 == 0 && ld_planes >= hidden && ld_planes % 4 == 0, CHATTS_E_SHAPE,
                  "rmsnorm_planes: hidden %d / ld_planes %d must be multiples of 4, ld_planes >= hidden", hidden, ld_planes);
-  hipLaunchKernelGGL(rmsnorm_kernel<true>, dim3(t), dim3(256), 0, as_stream(stream), x, w, nullptr, hidden, eps, hi, lo,
-                     ld_planes);
-  CHATTS_CHECK_LAUNCH("rmsnorm_planes");
-  return CHATTS_OK;
+  return launch_rmsnorm_planes(x, hidden, w, hi, lo, ld_planes, t, hidden, eps, as_stream(stream));
 }
 
 namespace chatts {

@@ -1086,9 +1086,8 @@ int launch_gemm(const ChattsLinearArgs* a_in, hipStream_t s, const RopeFuse* rop
                        a->ldc, a->epilogue, a->w8 ? a->w8_scale : nullptr, a->c_hi, a->c_lo, a->ld_cplanes);
     CHATTS_CHECK_LAUNCH("splitk_epilogue");
   }
-  if (post_norm)                  // no split-K epilogue to fuse into: the contract still holds, as its own launch
-    return chatts_rmsnorm_planes(a->c, a->post_norm_w, a->post_hi, a->post_lo, a->ld_post, a->m, a->n, a->post_norm_eps,
-                                 reinterpret_cast<chatts_stream_t>(s));
+  if (post_norm)                  // no split-K epilogue to fuse into: the contract still holds, as its own launch (rows of c ldc apart)
+    return launch_rmsnorm_planes(a->c, a->ldc, a->post_norm_w, a->post_hi, a->post_lo, a->ld_post, a->m, a->n, a->post_norm_eps, s);
   return CHATTS_OK;
 }
 

@@ -581,10 +581,11 @@ __device__ __forceinline__ void f16q_put4(const F16qPlanes& o, int row, int col,
   }
 }
 
-// RMSNorm with the row written as f16q planes (rmsnorm_kernel<true>'s arithmetic; one workgroup per row)
-__global__ __launch_bounds__(256) void rmsnorm_f16q_kernel(const float* __restrict__ x, const float* __restrict__ w, int hidden, float eps, F16qPlanes o) {
+// RMSNorm with the row written as f16q planes (rmsnorm_kernel<true>'s arithmetic; one workgroup per row; rows of x ldx floats apart)
+__global__ __launch_bounds__(256) void rmsnorm_f16q_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w, int hidden, float eps,
+                                                          F16qPlanes o) {
   __shared__ float red[4];
-  const float* xr = x + (size_t)blockIdx.x * hidden;
+  const float* xr = x + (size_t)blockIdx.x * ldx;
   float ss = 0.f;
   for (int k = threadIdx.x * 4; k < hidden; k += 1024) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(xr + k);
@@ -732,13 +733,13 @@ extern "C" int chatts_weights_f16q(const chatts_bf16* w, int n, int k, int ldw, 
 }
 
 
+// what the row-wise split-K epilogue below can take (chatts_linear_f16q decides the split count with it before launching anything)
+static bool f16q_splitk_epilogue_fits(const ChattsLinearF16qArgs* a) {
+  return a->n <= 8192 && a->n % 4 == 0 && (a->epilogue == CHATTS_EPI_NONE || a->epilogue == CHATTS_EPI_RESID) && !a->c_hi;
+}
+
 static int f16q_splitk_epilogue(const ChattsLinearF16qArgs* a, int sk, hipStream_t s) {
-  CHATTS_REQUIRE(sk <= 4 && a->n <= 8192 && a->n % 4 == 0 && a->epilogue != CHATTS_EPI_SWIGLU && a->epilogue != CHATTS_EPI_GELU, CHATTS_E_SHAPE,
-                 "linear_f16q: split-K epilogue handles <= 4 slabs of <= 8192 columns (EPI_NONE / EPI_RESID); got sk=%d n=%d", sk, a->n);
   F16qPlanes o{reinterpret_cast<_Float16*>(a->post_hi), a->post_lo8, a->post_scale, a->ld_post, a->ld_pscale, a->planes_tiled};
-  if (a->post_norm_w)
-    CHATTS_REQUIRE(o.hi && o.lo8 && o.sc && a->n % kF16qBlock == 0 && a->ld_post >= a->n && a->ld_post % 4 == 0 && a->ld_pscale >= a->n / kF16qBlock,
-                   CHATTS_E_SHAPE, "linear_f16q: post-norm planes need hi / lo8 / scale, N %% 128 == 0, ld_post >= N");
   const float* ws = reinterpret_cast<const float*>(a->workspace);
 #define CHATTS_EPI_Q(K) hipLaunchKernelGGL((splitk_epilogue_f16q_kernel<K>), dim3(a->m), dim3(256), 0, s, ws, sk, a->m, a->n, a->bias, a->resid, a->c, \
                                            a->ldc, a->epilogue, a->post_norm_w, a->post_norm_eps, o)
@@ -777,13 +778,13 @@ extern "C" int chatts_rmsnorm_f16q(const float* x, const float* w, chatts_f16* h
   CHATTS_REQUIRE(x && w && hi && lo8 && scale, CHATTS_E_BADARG, "rmsnorm_f16q: null pointer");
   CHATTS_REQUIRE(ld_planes >= hidden && ld_planes % 4 == 0 && ld_scale >= hidden / kF16qBlock, CHATTS_E_SHAPE, "rmsnorm_f16q: leading dimensions");
   F16qPlanes o{reinterpret_cast<_Float16*>(hi), lo8, scale, ld_planes, ld_scale, tiled};
-  hipLaunchKernelGGL(rmsnorm_f16q_kernel, dim3(t), dim3(256), 0, as_stream(stream), x, w, hidden, eps, o);
+  hipLaunchKernelGGL(rmsnorm_f16q_kernel, dim3(t), dim3(256), 0, as_stream(stream), x, hidden, w, hidden, eps, o);
   CHATTS_CHECK_LAUNCH("rmsnorm_f16q");
   return CHATTS_OK;
 }
 
 extern "C" size_t chatts_linear_f16q_workspace(int m, int n, int k) {
-  if (m < 1 || n < 1 || k < 128 || k % 128) return 0;
+  if (m < 1 || n < 1 || k < 128 || k % 128 || n > 8192) return 0;      // (wider than the split-K epilogue: never split)
   RingGeom g;
   f16q_pick(m, n, k, device_cus(), opt_get(OPT_GEMM_T, 0), opt_get(OPT_GEMM_SK, 0), g);
   return g.sk > 1 ? (size_t)g.sk * m * n * sizeof(float) : 0;
@@ -813,10 +814,16 @@ extern "C" int chatts_linear_f16q(const ChattsLinearF16qArgs* a, chatts_stream_t
     CHATTS_REQUIRE(a->c && a->ldc >= ncols && a->ldc % 4 == 0 && ((uintptr_t)a->c % 16) == 0, CHATTS_E_SHAPE, "linear_f16q: c / ldc=%d", a->ldc);
   CHATTS_REQUIRE(((uintptr_t)a->bias % 16) == 0 && ((uintptr_t)a->resid % 16) == 0, CHATTS_E_SHAPE, "linear_f16q: 16-byte aligned bias / resid");
   CHATTS_REQUIRE(a->epilogue != CHATTS_EPI_RESID || a->resid, CHATTS_E_BADARG, "linear_f16q: EPI_RESID without resid");
+  if (a->post_norm_w)                // checked here, before anything is enqueued: both the fused and the separate form write these planes
+    CHATTS_REQUIRE(a->c && !cplanes && (a->epilogue == CHATTS_EPI_NONE || a->epilogue == CHATTS_EPI_RESID) && a->post_hi && a->post_lo8 &&
+                       a->post_scale && a->n % kF16qBlock == 0 && a->ld_post >= a->n && a->ld_post % 4 == 0 && a->ld_pscale >= a->n / kF16qBlock,
+                   CHATTS_E_SHAPE, "linear_f16q: post-norm planes need float32 c, EPI_NONE / EPI_RESID, hi / lo8 / scale, N %% 128 == 0, ld_post >= N (%% 4)");
   RingGeom g;
   f16q_pick(a->m, a->n, a->k, device_cus(), opt_get(OPT_GEMM_T, 0), opt_get(OPT_GEMM_SK, 0), g);
   int sk = g.sk;
-  if (cplanes || a->epilogue == CHATTS_EPI_SWIGLU) sk = 1;          // (the SwiGLU output is large: never split)
+  // the split count is settled before the GEMM is enqueued: a call the split-K epilogue cannot take (SwiGLU - its output is large
+  // anyway -, GELU, N > 8192) runs direct
+  if (!f16q_splitk_epilogue_fits(a)) sk = 1;
   int kps = ((a->k / kF16qBlock + sk - 1) / sk) * kF16qBlock;
   sk = (a->k + kps - 1) / kps;
   g.sk = sk;
@@ -841,7 +848,10 @@ extern "C" int chatts_linear_f16q(const ChattsLinearF16qArgs* a, chatts_stream_t
   if (const int rc = launch_f16q(q, g, as_stream(stream))) return rc;
   CHATTS_CHECK_LAUNCH("gemm_f16q");
   if (sk > 1) return f16q_splitk_epilogue(a, sk, as_stream(stream));
-  if (a->post_norm_w)
-    return chatts_rmsnorm_f16q(a->c, a->post_norm_w, a->post_hi, a->post_lo8, a->post_scale, a->ld_post, a->ld_pscale, a->m, a->n, a->post_norm_eps, a->planes_tiled, stream);
+  if (a->post_norm_w) {              // no split-K epilogue to fuse into: its own launch, on the rows of c (ldc apart)
+    F16qPlanes o{reinterpret_cast<_Float16*>(a->post_hi), a->post_lo8, a->post_scale, a->ld_post, a->ld_pscale, a->planes_tiled};
+    hipLaunchKernelGGL(rmsnorm_f16q_kernel, dim3(a->m), dim3(256), 0, as_stream(stream), a->c, a->ldc, a->post_norm_w, a->n, a->post_norm_eps, o);
+    CHATTS_CHECK_LAUNCH("rmsnorm_f16q");
+  }
   return CHATTS_OK;
 }

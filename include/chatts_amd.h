@@ -155,7 +155,7 @@ typedef struct ChattsLinearArgs {
   const float* a;          /* [M, lda] */
   const chatts_bf16* w;    /* [N, ldw] */
   const float* bias;       /* [N] or NULL (for SWIGLU: interleaved like the rows) */
-  const float* resid;      /* EPI_RESID: [M, ldc] */
+  const float* resid;      /* EPI_RESID: [M, ldc] - the same row stride as c, also when c is NULL (plane output); may alias c */
   float* c;                /* [M, ldc]  (SWIGLU: [M, N/2]) */
   /* optional fused RMSNorm on the rows of A (decode path, M == 1 only):
    *   a_used[m,k] = norm_w[k] * (a[m,k] * rsqrt(mean_k(a[m,:]^2) + eps))   (Qwen2RMSNorm.forward) */
@@ -183,9 +183,10 @@ typedef struct ChattsLinearArgs {
   chatts_bf16* c_hi;
   chatts_bf16* c_lo;
   int ld_cplanes;
-  /* optional (M > 1, EPI_NONE / EPI_RESID, float32 c): additionally write RMSNorm(c) - rows of width N, weight
-   * post_norm_w, chatts_rmsnorm_planes arithmetic - as bf16 hi / lo planes [M, ld_post]: the operand of the projection that
-   * follows a residual update.  Fused into the split-K epilogue when there is one, otherwise an extra launch. */
+  /* optional (M > 1, EPI_NONE / EPI_RESID, float32 c): additionally write RMSNorm(c) - rows of width N read from c with its
+   * stride ldc (ldc % 4 == 0), weight post_norm_w, chatts_rmsnorm_planes arithmetic - as bf16 hi / lo planes [M, ld_post]: the
+   * operand of the projection that follows a residual update.  Fused into the split-K epilogue when there is one, otherwise an
+   * extra launch; the planes are the same bits either way. */
   const float* post_norm_w;
   float post_norm_eps;
   chatts_bf16* post_hi;
@@ -258,7 +259,8 @@ int chatts_linear(const ChattsLinearArgs* args, chatts_stream_t stream);
  * chatts_rmsnorm_f16q: chatts_rmsnorm's arithmetic with the row written as planes.  chatts_linear_f16q: the GEMM (M >= 1; meant for
  * prefill chunks); epilogues of chatts_linear; SWIGLU may write its result as planes (c_hi / c_lo8 / c_scale: the next projection's
  * operand) instead of float32 c; EPI_NONE / EPI_RESID may additionally write RMSNorm(c) as planes (post_*), fused into the split-K
- * epilogue when there is one.  Workspace: chatts_linear_f16q_workspace(m, n, k) bytes.
+ * epilogue when there is one.  Workspace: chatts_linear_f16q_workspace(m, n, k) bytes (never less than the call needs; 0 for N > 8192:
+ * the split-K epilogue takes EPI_NONE / EPI_RESID rows of <= 8192 columns, every other call runs without a split).
  * ------------------------------------------------------------------------------------------- */
 typedef struct ChattsLinearF16qArgs {
   const chatts_f16* a_hi;    /* [M, ld_a] */
@@ -270,14 +272,15 @@ typedef struct ChattsLinearF16qArgs {
   const uint8_t* w8_exp;     /* [N] e8m0 */
   int ldw;
   const float* bias;         /* [N] or NULL (SWIGLU: interleaved like the rows) */
-  const float* resid;        /* EPI_RESID: [M, ldc] */
+  const float* resid;        /* EPI_RESID: [M, ldc] - the same row stride as c; may alias c */
   float* c;                  /* [M, ldc] (SWIGLU: [M, N / 2]); may be NULL when c_hi is set */
   int m, n, k, ldc, epilogue;
   chatts_f16* c_hi;          /* optional (SWIGLU only): the result as f16q planes [M, ld_cplanes], scales [M, ld_cscale] */
   uint8_t* c_lo8;
   uint8_t* c_scale;
   int ld_cplanes, ld_cscale;
-  const float* post_norm_w;  /* optional (EPI_NONE / EPI_RESID): RMSNorm(c) with this weight as f16q planes */
+  const float* post_norm_w;  /* optional (EPI_NONE / EPI_RESID, N % 128 == 0): RMSNorm of the rows of c (read with stride ldc) with this
+                              * weight as f16q planes [M, ld_post], scales [M, ld_pscale]; fused into the split-K epilogue when there is one */
   float post_norm_eps;
   chatts_f16* post_hi;
   uint8_t* post_lo8;
@@ -324,7 +327,7 @@ typedef struct ChattsLinearFp8Args {
   const uint8_t* w8;       /* [N, ldw8] e4m3fn weights, row-major like ChattsLinearArgs.w8 */
   const float* w_scale;    /* [N] */
   const float* bias;       /* [N] or NULL (SWIGLU: interleaved like the rows) */
-  const float* resid;      /* EPI_RESID: [M, ldc]; may alias c */
+  const float* resid;      /* EPI_RESID: [M, ldc] - the same row stride as c; may alias c */
   float* c;                /* [M, ldc] float32 (SWIGLU: [M, N / 2]) */
   int m, n, k, lda8, ldw8, ldc, epilogue;      /* K % 128 == 0 (zero pad both operands); CHATTS_EPI_* */
 } ChattsLinearFp8Args;

@@ -270,3 +270,75 @@ def test_linear_f16q_on_tiled_operands_is_bitwise_the_row_major_result(lib, epi,
         pad = lambda t: torch.cat([t, torch.zeros((m16 - m, t.shape[1]), dtype=t.dtype, device=DEV)]) if m16 > m else t
         assert torch.equal(_tile16(pad(ph0)).view(torch.int16), ph1.view(-1).view(torch.int16))
         assert torch.equal(_tile8_rows16(pl0, m)[0], pl1.view(-1)) and torch.equal(ps0, ps1)
+
+
+# ---- forced geometries, the GELU epilogue, N > 8192 and the workspace contract -------------------------------------------------------------
+def _f16q_check(lib, O, epi, post=False, what=""):
+    """the call with the queried workspace against f16q_ref.gemm (2e-6) and the true product (3e-5), post-norm planes == the split of
+    chatts_rmsnorm(c); then the workspace contract: 16 bytes fewer than the query is refused (c untouched) unless the call needs none"""
+    from tests.test_gpu_strides import F16Q_DENSE, _f16q_call, _f16q_post_ref, _f16q_refs, untouched
+    rc, outs, wsb = _f16q_call(lib, O, epi, F16Q_DENSE, post=post)
+    _lib.check(rc)
+    out = outs["c"][0]
+    ref, true = _f16q_refs(O, epi)
+    assert not torch.isnan(out).any(), what
+    assert rel_err(out.cpu().numpy(), ref) < 2e-6, what
+    assert rel_err(out.cpu().numpy(), true) < 3e-5, what
+    if post:
+        eh, eq, es = _f16q_post_ref(lib, out, O["post"])
+        ph, pl, ps = (outs[name][0] for name in ("post_hi", "post_lo8", "post_scale"))
+        assert torch.equal(eh.view(torch.int16), ph.view(torch.int16)) and torch.equal(eq, pl) and torch.equal(es, ps), what
+    if wsb > 0:
+        rc, short, _ = _f16q_call(lib, O, epi, F16Q_DENSE, post=post, ws_delta=-16)
+        if epi in (_lib.EPI_NONE, _lib.EPI_RESID) and O["w"].shape[0] <= 8192:     # (these calls split exactly as the query assumed)
+            assert rc == _lib.E_WORKSPACE, (what, rc)
+        if rc == _lib.E_WORKSPACE:
+            assert all(untouched(buf) for buf, _ in short.values()), what           # refused: nothing was enqueued
+        else:
+            _lib.check(rc)
+            assert torch.equal(short["c"][0], out), what
+
+
+@pytest.mark.parametrize("sk", [1, 2, 3, 4])
+@pytest.mark.parametrize("t", ["min", "mid", "F"])
+def test_linear_f16q_forced_geometries(lib, monkeypatch, t, sk):
+    """GEMM_T (tiles across the rows: the fewest the 9-fragment accumulators allow - 9 fragments per tile at M = 272, gemm_f16q_kernel<5> -,
+    a middle count, one 16-row fragment per tile) x GEMM_SK 1..4: every geometry within the float64 bars, with and without post-norm,
+    EPI_NONE and EPI_RESID (split-K changes the order of the sums: each geometry is held to the bars, not to the others' bits)"""
+    from tests.test_gpu_strides import _f16q_operands
+    m, n, k = 272, 512, 1024
+    F = (m + 15) // 16
+    tmin = (F + 8) // 9
+    assert (F + tmin - 1) // tmin == 9
+    monkeypatch.setenv("CHATTS_GEMM_T", str({"min": tmin, "mid": (tmin + F) // 2, "F": F}[t]))
+    monkeypatch.setenv("CHATTS_GEMM_SK", str(sk))
+    O = _f16q_operands(lib, m, n, k, seed=17 + sk, tiled=False)
+    for epi in (_lib.EPI_NONE, _lib.EPI_RESID):
+        for post in (False, True):
+            _f16q_check(lib, O, epi, post, what=f"T={t} sk={sk} epi={epi} post={post}")
+
+
+@pytest.mark.parametrize("sk", [None, 2])
+def test_linear_f16q_gelu_epilogue(lib, monkeypatch, sk):
+    """EPI_GELU at a shape where the picker splits K (few tiles, long K), at the picker's choice and with GEMM_SK forced to 2: the
+    split-K epilogue has no GELU form, so the call must not split (and must not fail after enqueueing the GEMM)"""
+    from tests.test_gpu_strides import _f16q_operands
+    m, n, k = 96, 512, 5120
+    assert lib.chatts_linear_f16q_workspace(m, n, k) > 0                  # the picker would split this shape
+    if sk:
+        monkeypatch.setenv("CHATTS_GEMM_SK", str(sk))
+    _f16q_check(lib, _f16q_operands(lib, m, n, k, seed=23, tiled=False), _lib.EPI_GELU, what=f"gelu sk={sk}")
+
+
+@pytest.mark.parametrize("sk", [None, 2])
+@pytest.mark.parametrize("epi", [_lib.EPI_NONE, _lib.EPI_RESID])
+def test_linear_f16q_wider_than_the_split_epilogue(lib, monkeypatch, epi, sk):
+    """N = 10240 > 8192 (the row-wise split-K epilogue's limit, e.g. a wide qkv projection): the call takes the direct path whatever the
+    picker or GEMM_SK say, with and without post-norm"""
+    from tests.test_gpu_strides import _f16q_operands
+    m, n, k = 96, 10240, 1024
+    if sk:
+        monkeypatch.setenv("CHATTS_GEMM_SK", str(sk))
+    O = _f16q_operands(lib, m, n, k, seed=29 + epi, tiled=False)
+    for post in (False, True):
+        _f16q_check(lib, O, epi, post, what=f"n=10240 epi={epi} sk={sk} post={post}")
