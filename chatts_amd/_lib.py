@@ -96,6 +96,12 @@ class SamplingArgs(C.Structure):
                 ("seed_rows", c_void_p)]
 
 
+class LogitControlArgs(C.Structure):
+    _fields_ = [("state", c_void_p), ("state_stride", c_int64), ("out", c_void_p), ("out_stride", c_int64),
+                ("repetition_rows", c_void_p), ("frequency_rows", c_void_p), ("presence_rows", c_void_p), ("min_p_rows", c_void_p),
+                ("temperature_rows", c_void_p)]
+
+
 class DecoderConfig(C.Structure):
     _fields_ = [("hidden", c_int), ("n_layers", c_int), ("n_q", c_int), ("n_kv", c_int), ("head_dim", c_int),
                 ("inter", c_int), ("vocab_local", c_int64), ("vocab_offset", c_int64), ("rms_eps", c_float),
@@ -203,6 +209,16 @@ SIGNATURES = {
     "chatts_decoder_set_tp": (c_int, [c_void_p, c_void_p]),
     "chatts_decoder_select_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                              c_void_p, c_int, C.POINTER(SamplingArgs), c_void_p]),
+    "chatts_decoder_select_tokens_controlled": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                        c_void_p, c_void_p, c_int, C.POINTER(SamplingArgs),
+                                                        C.POINTER(LogitControlArgs), c_void_p]),
+    "chatts_decoder_set_logit_controls": (c_int, [c_void_p, C.POINTER(LogitControlArgs)]),
+    # logit controls (logit_controls.hip)
+    "chatts_logit_controls_workspace": (c_size_t, [c_int]),
+    "chatts_logit_controls_apply": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, C.POINTER(LogitControlArgs), c_void_p, c_size_t,
+                                            c_void_p]),
+    "chatts_logit_state_reset": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "chatts_logit_state_update": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     # tensor-parallel exchange (tp.hip)
     "chatts_tp_buffer_bytes": (c_size_t, [c_int, c_int64]),
     "chatts_tp_buffer_bytes_bulk": (c_size_t, [c_int, c_int64, c_int64]),

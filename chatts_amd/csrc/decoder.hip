@@ -37,6 +37,8 @@ struct ChattsDecoder {
                             // projection's fused epilogue): norm_into only binds them
   bool sampling = false;    // token selection of the decode steps: greedy argmax, or the sampler with `sa`
   ChattsSamplingArgs sa{};
+  bool controls = false;    // logit controls (penalties / min_p) ahead of every selection, with `lc` (chatts_decoder_set_logit_controls)
+  ChattsLogitControlArgs lc{};
   ChattsTpComm* tp = nullptr;   // tensor-parallel exchange (borrowed); required by the whole-step entry points when tp_world > 1
   bool prefill_f16q = false; // opt-in parity-grade mode (chatts_decoder_set_prefill_f16q): prefill chunks of >= 96 rows on the f16 + e4m3 operand split
   bool normed_q = false;    // the f16q planes A already hold RMSNorm(x) for the projection that comes next (layer_part_f16q only)
@@ -250,15 +252,74 @@ extern "C" int chatts_decoder_set_tp(ChattsDecoder* d, ChattsTpComm* comm) {
   return CHATTS_OK;
 }
 
-// Greedy / sampled token for `batch` logits rows of this rank, agreed across the TP ranks (see the header).
+extern "C" int chatts_decoder_set_logit_controls(ChattsDecoder* d, const ChattsLogitControlArgs* lc) {
+  CHATTS_REQUIRE(d, CHATTS_E_BADARG, "decoder_set_logit_controls: null decoder");
+  if (lc) CHATTS_REQUIRE(lc->state && lc->out, CHATTS_E_BADARG, "decoder_set_logit_controls: args.state and args.out are required");
+  d->controls = lc != nullptr;
+  if (lc) d->lc = *lc;
+  return CHATTS_OK;
+}
+
+// Selection with the logit controls on: penalised logits into lc->out, the TP = 1 selection on them, the chosen tokens into the state.
+// Tensor parallel: every rank gathers the full-vocabulary logits and does the same work on the same bytes -> the same token.
+static int select_controlled(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride, int64_t* token, float* token_logit,
+                             int64_t* out_tokens, int64_t out_stride, int32_t* step_dev, int32_t* pos_dev, int pos_limit,
+                             const ChattsSamplingArgs* sa, const ChattsLogitControlArgs* lc, chatts_stream_t stream) {
+  const ChattsDecoderConfig& c = d->cfg;
+  int64_t vocab = c.vocab_local, offset = c.vocab_offset;
+  int rc;
+  if (c.tp_world > 1) {
+    CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "decoder_select_tokens: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", c.tp_world);
+    const int mb = d->b.max_batch > 0 ? d->b.max_batch : 1;
+    CHATTS_REQUIRE(batch <= mb, CHATTS_E_SHAPE, "decoder_select_tokens: batch %d exceeds max_batch %d", batch, mb);
+    CHATTS_REQUIRE(d->b.logits_full, CHATTS_E_BADARG, "decoder_select_tokens: logit controls under tensor parallelism need buffers.logits_full");
+    CHATTS_REQUIRE(logits_stride == c.vocab_local || batch == 1, CHATTS_E_SHAPE, "decoder_select_tokens: logits rows must be contiguous");
+    vocab = c.vocab_local * c.tp_world; offset = 0;
+  }
+  // validate before the collective: a refusal on one rank must not leave the others waiting in it
+  CHATTS_REQUIRE(lc->state && lc->out && lc->state_stride >= vocab && lc->out_stride >= vocab, CHATTS_E_BADARG,
+                 "decoder_select_tokens: logit controls need state and out rows of >= %lld cells", (long long)vocab);
+  CHATTS_REQUIRE(d->b.workspace && d->b.workspace_bytes >= chatts_logit_controls_workspace(batch), CHATTS_E_WORKSPACE,
+                 "decoder_select_tokens: the workspace is too small for the logit controls of %d rows", batch);
+  if (c.tp_world > 1) {
+    if ((rc = chatts_allgather(d->tp, logits, d->b.logits_full, batch, c.vocab_local, stream)) != 0) return rc;
+    logits = d->b.logits_full; logits_stride = vocab;
+  }
+  // (the split-K / attention workspace is idle here: every kernel that used it is ahead of this call on the stream)
+  if ((rc = chatts_logit_controls_apply(logits, batch, logits_stride, vocab, offset, lc, d->b.workspace, d->b.workspace_bytes, stream)) != 0)
+    return rc;
+  if (sa)
+    rc = chatts_sample_batched(lc->out, batch, lc->out_stride, vocab, offset, sa, token, token_logit, out_tokens, out_stride, step_dev,
+                               pos_dev, pos_limit, stream);
+  else
+    rc = chatts::argmax_batched_scratch(lc->out, batch, lc->out_stride, vocab, offset, token, token_logit, out_tokens, out_stride, step_dev,
+                                        pos_dev, pos_limit, d->b.workspace, d->b.workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  if (rc) return rc;
+  return chatts_logit_state_update(lc->state, lc->state_stride, batch, vocab, offset, token, stream);
+}
+
 extern "C" int chatts_decoder_select_tokens(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride, int64_t* token,
                                             float* token_logit, int64_t* out_tokens, int64_t out_stride, int32_t* step_dev,
                                             int32_t* pos_dev, int pos_limit, const ChattsSamplingArgs* override_sa,
                                             chatts_stream_t stream) {
+  return chatts_decoder_select_tokens_controlled(d, logits, batch, logits_stride, token, token_logit, out_tokens, out_stride, step_dev,
+                                                 pos_dev, pos_limit, override_sa, nullptr, stream);
+}
+
+// Greedy / sampled token for `batch` logits rows of this rank, agreed across the TP ranks (see the header).
+extern "C" int chatts_decoder_select_tokens_controlled(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride,
+                                                       int64_t* token, float* token_logit, int64_t* out_tokens, int64_t out_stride,
+                                                       int32_t* step_dev, int32_t* pos_dev, int pos_limit,
+                                                       const ChattsSamplingArgs* override_sa, const ChattsLogitControlArgs* override_lc,
+                                                       chatts_stream_t stream) {
   CHATTS_REQUIRE(d && logits && token && batch >= 1, CHATTS_E_BADARG, "decoder_select_tokens: bad arguments");
   StageRange stage("chatts.select_tokens");
   const ChattsDecoderConfig& c = d->cfg;
   const ChattsSamplingArgs* sa = override_sa ? override_sa : (d->sampling ? &d->sa : nullptr);
+  const ChattsLogitControlArgs* lc = override_lc ? override_lc : (d->controls ? &d->lc : nullptr);
+  if (lc)
+    return select_controlled(d, logits, batch, logits_stride, token, token_logit, out_tokens, out_stride, step_dev, pos_dev, pos_limit, sa,
+                             lc, stream);
   if (c.tp_world <= 1) {
     if (sa)
       return chatts_sample_batched(logits, batch, logits_stride, c.vocab_local, c.vocab_offset, sa, token, token_logit, out_tokens,

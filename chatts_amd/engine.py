@@ -19,11 +19,38 @@ from collections import deque
 import numpy as np
 
 
-def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, logprobs=None, max_logprobs=20, prompt_logprobs=None, **_):
+def validate_controls(repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None):
+    """The four logit controls with vLLM's defaults and ranges -> (r, f, p, min_p) as floats (None = the default); ValueError otherwise."""
+    import math
+    vals = []
+    for name, v, default in (("repetition_penalty", repetition_penalty, 1.0), ("frequency_penalty", frequency_penalty, 0.0),
+                             ("presence_penalty", presence_penalty, 0.0), ("min_p", min_p, 0.0)):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        vals.append(float(v))
+    r, f, p, m = vals
+    if not r > 0.0:
+        raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
+    if not -2.0 <= f <= 2.0:
+        raise ValueError(f"frequency_penalty must be in [-2, 2], got {frequency_penalty}")
+    if not -2.0 <= p <= 2.0:
+        raise ValueError(f"presence_penalty must be in [-2, 2], got {presence_penalty}")
+    if not 0.0 <= m <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], got {min_p}")
+    return r, f, p, m
+
+
+NO_CONTROLS = (1.0, 0.0, 0.0, 0.0)
+
+
+def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, logprobs=None, max_logprobs=20, prompt_logprobs=None,
+                      repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None, **_):
     """The ranges vLLM's SamplingParams accepts (what the reference's drivers pass: inference_tsmllm_vllm.py:43-46,
     llm_utils.py:153).  Raises ValueError - the server turns it into a 400 - BEFORE the request can reach the engine thread, where
     an out-of-range value would otherwise surface inside set_sampling / chatts_decoder_set_sampling."""
     import math
+    validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
     t = 0.0 if temperature is None else float(temperature)
     if not math.isfinite(t) or t < 0.0:
         raise ValueError(f"temperature must be a finite number >= 0, got {temperature}")
@@ -57,6 +84,7 @@ class Request:
         self.logprob_k, self.logprobs, self.cumulative_logprob = None, None, None
         self.t_arrival, self.t_first = time.perf_counter(), None
         self.error = None
+        self.controls = NO_CONTROLS          # (repetition_penalty, frequency_penalty, presence_penalty, min_p): Engine.add_request
         self.bypassed = 0                    # later arrivals admitted past this request while it waited for its sampling group
 
 
@@ -71,6 +99,7 @@ class Engine:
         self.greedy_return_steps = max(0, int(greedy_return_steps))
         self._greedy_iters = 0
         self._no_logprob_iters = 0
+        self._no_control_iters = 0
         self.sync_every = max(1, int(sync_every))       # decode steps between device->host token reads
         # chunked-prefill scheduling (vLLM: enable_chunked_prefill / max_num_batched_tokens): while other sequences are decoding, a
         # long prompt is prefilled this many rows per scheduler iteration, each followed by one decode step of the running batch,
@@ -91,11 +120,15 @@ class Engine:
 
     # ---- requests ---------------------------------------------------------------------------------
     def add_request(self, prompt, timeseries=None, max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, seed=None,
-                    stop_token_ids=None, ignore_eos=False, on_tokens=None, logprobs=None):
+                    stop_token_ids=None, ignore_eos=False, on_tokens=None, logprobs=None, repetition_penalty=None,
+                    frequency_penalty=None, presence_penalty=None, min_p=None):
         """seed None: per-slot mode gives every request its own stream (a hash of its arrival number - vLLM's seed=None means "not
         reproducible across requests"; here two identical prompts still differ, and a rerun of the same arrival order repeats);
         grouped mode uses 0 (requests that decode together must share ONE configuration there)."""
         validate_sampling(max_tokens, temperature, top_p, top_k, logprobs=logprobs, max_logprobs=self.max_logprobs)
+        controls = validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
+        if controls != NO_CONTROLS and not hasattr(self.model, "set_slot_controls"):
+            raise ValueError("this model does not apply repetition / frequency / presence penalties or min_p")
         if logprobs is not None and not hasattr(self.model, "set_logprobs"):
             raise ValueError("this model does not compute logprobs")
         if seed is None:
@@ -107,6 +140,7 @@ class Engine:
         self._rid += 1
         r = Request(self._rid, prompt, list(timeseries or []), max_tokens, key, eos, on_tokens)
         r.sampling = (0.0, 0, 1.0, 0) if key is None else key
+        r.controls = controls                # (repetition_penalty, frequency_penalty, presence_penalty, min_p)
         if logprobs is not None:
             r.logprob_k, r.logprobs, r.cumulative_logprob = int(logprobs), [], 0.0
         if self.mixed:
@@ -136,6 +170,24 @@ class Engine:
             self._no_logprob_iters += 1
             if self.greedy_return_steps and self._no_logprob_iters >= self.greedy_return_steps:
                 self.model.set_logprobs(False)
+
+    def _controls_mode(self):
+        """The model's logit-controls mode on while any running, prefilling or waiting request has a penalty or min_p; off again after
+        `greedy_return_steps` consecutive iterations without one (the hysteresis of _logprobs_mode, for the same reason)."""
+        if not hasattr(self.model, "set_logit_controls"):
+            return
+        want = (any(r is not None and r.controls != NO_CONTROLS for r in self.slots) or
+                (self.prefilling is not None and self.prefilling[0].controls != NO_CONTROLS) or
+                any(q.controls != NO_CONTROLS for q in self.waiting))
+        on = bool(getattr(self.model, "_controls_on", False))
+        if want:
+            self._no_control_iters = 0
+            if not on:
+                self.model.set_logit_controls(True)
+        elif on:
+            self._no_control_iters += 1
+            if self.greedy_return_steps and self._no_control_iters >= self.greedy_return_steps:
+                self.model.set_logit_controls(False)
 
     def has_work(self):
         return bool(self.waiting) or self.prefilling is not None or any(s is not None for s in self.slots)
@@ -195,6 +247,7 @@ class Engine:
         if self.mixed:
             self._mixed_mode()
         self._logprobs_mode()
+        self._controls_mode()
         while not self.mixed and not running and self.waiting and self.waiting[0].sampling_key != self.active_key:
             try:
                 self._apply_sampling(self.waiting[0].sampling_key)
@@ -272,6 +325,8 @@ class Engine:
                 self.waiting.remove(r)
                 if self.mixed:                           # the slot's settings, before its first token is drawn
                     m.set_slot_sampling(s, *r.sampling)
+                    if hasattr(m, "set_slot_controls"):
+                        m.set_slot_controls(s, *r.controls)
             try:
                 if len(items) > 1:
                     m._admit_packed(items)               # several short prompts: one packed prefill pass
@@ -510,7 +565,8 @@ class EngineThread:
         ok = []
         for kw in new:
             try:
-                validate_sampling(**{k: kw[k] for k in ("max_tokens", "temperature", "top_p", "top_k", "logprobs") if k in kw},
+                validate_sampling(**{k: kw[k] for k in ("max_tokens", "temperature", "top_p", "top_k", "logprobs", "repetition_penalty",
+                                                          "frequency_penalty", "presence_penalty", "min_p") if k in kw},
                                   max_logprobs=getattr(self.engine, "max_logprobs", 20))
                 ok.append(kw)
             except (ValueError, TypeError) as e:

@@ -11,7 +11,9 @@ import numpy as np
 
 class SamplingParams:
     def __init__(self, max_tokens=16, temperature=0.0, top_p=1.0, top_k=-1, seed=None, stop_token_ids=None,
-                 ignore_eos=False, logprobs=None, prompt_logprobs=None, **kw):
+                 ignore_eos=False, logprobs=None, prompt_logprobs=None, repetition_penalty=1.0, frequency_penalty=0.0,
+                 presence_penalty=0.0, min_p=0.0, **kw):
+        from .engine import validate_controls
         if prompt_logprobs is not None:
             raise ValueError("prompt_logprobs is not supported (only the logprobs of generated tokens: logprobs=k)")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or logprobs < 0):
@@ -24,6 +26,10 @@ class SamplingParams:
         self.seed = seed
         self.stop_token_ids = list(stop_token_ids or [])
         self.ignore_eos = ignore_eos
+        # vLLM's names, defaults and ranges: l / r (l > 0) or l * r for ids of the prompt or the output; l -= f * count and l -= p for
+        # ids of the output; min_p drops ids less probable than min_p x the most probable one (sampled requests only)
+        self.repetition_penalty, self.frequency_penalty, self.presence_penalty, self.min_p = validate_controls(
+            repetition_penalty, frequency_penalty, presence_penalty, min_p)
 
 
 class Logprob:
@@ -155,8 +161,11 @@ class LLM:
         if sp.logprobs is not None and sp.logprobs > self.model.max_logprobs:
             raise ValueError(f"logprobs={sp.logprobs} exceeds max_logprobs={self.model.max_logprobs} (LLM(max_logprobs=...))")
         self.model.set_logprobs(sp.logprobs is not None)      # per call, like the sampling mode (a switch re-captures the graphs)
+        controls = (sp.repetition_penalty, sp.frequency_penalty, sp.presence_penalty, sp.min_p)
+        if controls == (1.0, 0.0, 0.0, 0.0):
+            self.model.set_logit_controls(False)              # per call too: a default call runs the plain selection
         self.model.set_sampling(sp.temperature or 0.0, max(int(sp.top_k or 0), 0), sp.top_p,
-                                self._seed if sp.seed is None else sp.seed)
+                                self._seed if sp.seed is None else sp.seed, *controls)
         if isinstance(prompts, (str, dict)):
             prompts = [prompts]
         import torch

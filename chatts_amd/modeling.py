@@ -204,6 +204,9 @@ class ChatTSForCausalLM:
         # rings [max_batch, out_stride(, K)] allocated on first use; a request reads the first k <= max_logprobs of its cells
         self.max_logprobs = int(max_logprobs)
         self._logprobs_on = False
+        # logit controls (set_logit_controls): repetition / frequency / presence penalties and min_p ahead of every selection, from
+        # per-slot arrays and a per-slot state [max_batch, vocab] allocated on first use
+        self._controls_on = False
         self.layers = []
         self.loaded = set()
 
@@ -832,9 +835,16 @@ class ChatTSForCausalLM:
             last = 1 if (fast_last and final) else n
         return last
 
-    def set_sampling(self, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    def set_sampling(self, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=None, frequency_penalty=None,
+                     presence_penalty=None, min_p=None):
         """Token selection of every following step: greedy (temperature 0 / None, the default) or temperature / top-k /
-        top-p sampling on the GPU (chatts_sample_batched).  Same seed + same prompt => same tokens."""
+        top-p sampling on the GPU (chatts_sample_batched).  Same seed + same prompt => same tokens.  The four logit controls: when any
+        is given, all four are set for every cache slot (set_slot_controls; one not given = its default); when none is, the slots keep
+        theirs."""
+        if any(v is not None for v in (repetition_penalty, frequency_penalty, presence_penalty, min_p)):
+            self.set_slot_controls(None, repetition_penalty, frequency_penalty, presence_penalty, min_p)
+        if "lc_temp" in self.buf:
+            self.buf["lc_temp"].fill_(float(temperature or 0.0))
         if not temperature:
             args = None
         else:
@@ -873,20 +883,115 @@ class ChatTSForCausalLM:
         args = self._rows_args(0)
         _lib.check(self.lib.chatts_decoder_set_sampling(self._decoder, C.byref(args)))
         self._sampling, self._sampling_key = args, "rows"
+        if "lc_temp" in self.buf:
+            self.buf["lc_temp"].copy_(self.buf["samp_temp"])
         self._drop_graphs()
 
-    def set_slot_sampling(self, slot, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    def set_slot_sampling(self, slot, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0, frequency_penalty=0.0,
+                          presence_penalty=0.0, min_p=0.0):
         """Sampling settings of the sequence in cache slot `slot`: used by every step in per-slot mode (set_sampling_rows), inert in
-        the other modes.  A plain device write - no re-capture."""
+        the other modes.  A plain device write - no re-capture.  The four logit controls: set_slot_controls."""
         temperature = 0.0 if temperature is None else float(temperature)
         if temperature < 0 or not (0.0 < top_p <= 1.0):
             raise ValueError(f"temperature={temperature} must be >= 0 and top_p={top_p} in (0, 1]")
+        self.set_slot_controls(slot, repetition_penalty, frequency_penalty, presence_penalty, min_p)
         B = self._sampling_arrays()
+        if "lc_temp" in B and getattr(self, "_sampling_key", None) == "rows":
+            B["lc_temp"][slot] = temperature
         B["samp_temp"][slot] = temperature
         B["samp_topk"][slot] = max(int(top_k or 0), 0)
         B["samp_topp"][slot] = float(top_p)
         s32 = int(seed) & 0xFFFFFFFF
         B["samp_seed"][slot] = s32 - (1 << 32) if s32 >= (1 << 31) else s32
+
+    # ---- logit controls: repetition / frequency / presence penalties and min_p (csrc/logit_controls.hip) ----------------------------
+    @staticmethod
+    def check_controls(repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None):
+        """-> the four values as floats (None = the default); ValueError outside vLLM's ranges (engine.validate_controls)"""
+        from .engine import validate_controls
+        return validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
+
+    def _control_buffers(self):
+        B = self.buf
+        if "lc_state" not in B:
+            dev, n, V = self.device, max(1, self.max_batch), self.plan.vocab * self.plan.world
+            B["lc_state"] = torch.zeros((n, V), dtype=torch.int32, device=dev)     # bit 30: in the prompt; bits 0..29: times generated
+            B["lc_out"] = torch.zeros((n, V), dtype=torch.float32, device=dev)     # the penalised logits the selection reads
+            B["lc_rep"] = torch.ones(n, dtype=torch.float32, device=dev)
+            B["lc_freq"] = torch.zeros(n, dtype=torch.float32, device=dev)
+            B["lc_pres"] = torch.zeros(n, dtype=torch.float32, device=dev)
+            B["lc_minp"] = torch.zeros(n, dtype=torch.float32, device=dev)
+            B["lc_temp"] = torch.zeros(n, dtype=torch.float32, device=dev)         # the temperature each slot is sampled with (min_p cut)
+            key, sa = getattr(self, "_sampling_key", None), getattr(self, "_sampling", None)
+            if key == "rows":
+                B["lc_temp"].copy_(B["samp_temp"])
+            elif sa is not None:
+                B["lc_temp"].fill_(float(sa.temperature))
+        return B
+
+    def _control_args(self, slot):
+        B = self._control_buffers()
+        V = B["lc_state"].shape[1]
+        return _lib.LogitControlArgs(state=B["lc_state"][slot:].data_ptr(), state_stride=V, out=B["lc_out"][slot:].data_ptr(), out_stride=V,
+                                     repetition_rows=B["lc_rep"][slot:].data_ptr(), frequency_rows=B["lc_freq"][slot:].data_ptr(),
+                                     presence_rows=B["lc_pres"][slot:].data_ptr(), min_p_rows=B["lc_minp"][slot:].data_ptr(),
+                                     temperature_rows=B["lc_temp"][slot:].data_ptr())
+
+    def set_logit_controls(self, on):
+        """Logit controls on / off for every following selection.  On: each selection (decode steps, first tokens of every admission
+        path) first writes the penalised logits of its rows (repetition / frequency / presence penalties from the per-slot state, the
+        min_p cut) to a buffer of their own, selects from those, and counts the chosen tokens into the state; the raw logits - and so the
+        logprobs - are untouched.  A switch drops the captured decode graphs; off, the steps are exactly what they are without the
+        feature.  set_slot_controls switches it on when a slot needs it; the engine switches it off after greedy_return_steps
+        iterations without a request that does."""
+        on = bool(on)
+        if on == self._controls_on:
+            return
+        if on and self.plan.world > 1 and self._tp is None:
+            raise NotImplementedError("repetition / frequency / presence penalties and min_p under tensor parallelism need the "
+                                      "peer-to-peer exchange (use_p2p=True)")
+        if on:
+            args = self._control_args(0)
+            _lib.check(self.lib.chatts_decoder_set_logit_controls(self._decoder, C.byref(args)))
+        else:
+            _lib.check(self.lib.chatts_decoder_set_logit_controls(self._decoder, None))
+        self._controls_on = on
+        self._drop_graphs()
+
+    def set_slot_controls(self, slot, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, min_p=0.0):
+        """Logit controls of the sequence in cache slot `slot` (None: of every slot), with vLLM's names, defaults and ranges: plain
+        device writes, no re-capture.  Values other than the defaults switch the mode on (set_logit_controls); all-default values never
+        allocate anything."""
+        r, f, p, m = self.check_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
+        if (r, f, p, m) != (1.0, 0.0, 0.0, 0.0):
+            self.set_logit_controls(True)
+        elif "lc_rep" not in self.buf:
+            return
+        B = self.buf
+        for key, v in (("lc_rep", r), ("lc_freq", f), ("lc_pres", p), ("lc_minp", m)):
+            if slot is None:
+                B[key].fill_(v)
+            else:
+                B[key][slot] = v
+
+    def _request_controls(self, controls, n):
+        """controls argument of generate_batch -> one checked dict or None per request"""
+        per = list(controls) if isinstance(controls, (list, tuple)) else [controls] * n
+        if len(per) != n:
+            raise ValueError("controls: one value per request")
+        for c in per:
+            if c is not None:
+                self.check_controls(**c)
+        return per
+
+    def _controls_admit(self, slot, ids):
+        """(controls on) a request enters cache slot `slot`: clear the slot's state and mark its prompt ids"""
+        if not self._controls_on:
+            return
+        B = self.buf
+        prompt = torch.tensor(list(ids), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.chatts_logit_state_reset(B["lc_state"][slot].data_ptr(), B["lc_state"].shape[1], 0,
+                                                     _lib.ptr(prompt) if prompt.numel() else None, prompt.numel(), _lib.stream_ptr()))
 
     def set_logprobs(self, on):
         """Token logprobs on / off for every following selection.  On: each selection (decode steps, first tokens of every admission
@@ -948,6 +1053,8 @@ class ChatTSForCausalLM:
         if self.plan.world == 1 or self._tp is not None:
             self._select_one(0, 0, None)
             return
+        if self._controls_on:
+            raise NotImplementedError("logit controls are not available on the host-driven tensor-parallel path (use_p2p=False)")
         lib, st, B = self.lib, _lib.stream_ptr(), self.buf
         self._select_token_host_tp()
         if self._logprobs_on:     # every rank: the same kernel on the same gathered logits
@@ -962,10 +1069,18 @@ class ChatTSForCausalLM:
         """chatts_decoder_select_tokens on the logits of one row -> the sequence in cache slot `slot` (+ its logprobs).
         sampling: SamplingArgs for this call, None = the decoder's own setting."""
         B = self.buf
-        _lib.check(self.lib.chatts_decoder_select_tokens(
-            self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
-            B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), out_stride,
-            B["step_all"][slot:].data_ptr(), None, 0, None if sampling is None else C.byref(sampling), _lib.stream_ptr()))
+        sa = None if sampling is None else C.byref(sampling)
+        if self._controls_on:          # this single-row call sees row 0: hand it the slot's state and settings
+            lc = self._control_args(slot)
+            _lib.check(self.lib.chatts_decoder_select_tokens_controlled(
+                self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
+                B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), out_stride,
+                B["step_all"][slot:].data_ptr(), None, 0, sa, C.byref(lc), _lib.stream_ptr()))
+        else:
+            _lib.check(self.lib.chatts_decoder_select_tokens(
+                self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
+                B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), out_stride,
+                B["step_all"][slot:].data_ptr(), None, 0, sa, _lib.stream_ptr()))
         self._logprobs_after(B["logits"], 1, slot)
 
     def _select_token_host_tp(self):
@@ -1031,6 +1146,8 @@ class ChatTSForCausalLM:
     def _capture_graph(self, step_fn, keys, warm=True):
         """-> a graph of step_fn(); the buffers `keys` (the decode-loop state step_fn advances) are left as they were."""
         B = self.buf
+        if self._controls_on:
+            keys = tuple(keys) + ("lc_state",)      # the selection counts its tokens into the state
         saved = {k: B[k].clone() for k in keys}
         torch.cuda.synchronize()
         if warm:
@@ -1187,6 +1304,7 @@ class ChatTSForCausalLM:
         """First half of an admission into cache slot `slot`: TS encoder, prompt expansion, embeddings, KV reservation and prefix
         reuse - everything but the prefill itself.  -> the state admit_step() consumes."""
         T, emb, idents, _, _ = self._prepare_request(ids, series, lengths, max_new_tokens)
+        self._controls_admit(slot, ids)
         self.reserve_kv(slot, T + max_new_tokens, idents)
         n0 = self._reuse_prefix(slot, idents, T)
         self._slot_idents[slot] = []                # not a prefix source for others until all of its rows exist
@@ -1291,6 +1409,7 @@ class ChatTSForCausalLM:
                 raise
         for slot, ids, series, lengths, max_new in items:
             T, emb, idents, series, lengths = self._prepare_request(ids, series, lengths, max_new)
+            self._controls_admit(slot, ids)
             # reuse from ANY slot, the member's own and other members' included: every K/V row copy is enqueued here, i.e. before
             # the packed pass overwrites anything; a slot stops being a source once its member has been processed (idents cleared)
             self.reserve_kv(slot, T + max_new, idents)       # (dynamic pool: already covered by the pre-pass above)
@@ -1321,11 +1440,14 @@ class ChatTSForCausalLM:
         return Ts
 
     @torch.no_grad()
-    def generate_batch(self, requests, max_new_tokens=64, eos_token_id=None, sync_every=8, logprobs=None):
+    def generate_batch(self, requests, max_new_tokens=64, eos_token_id=None, sync_every=8, logprobs=None, controls=None):
         """Continuous batching over `max_batch` cache slots.  requests: list of (ids, series [n,2Lmax,1] | None,
         lengths | None).  A finished sequence frees its slot for the next waiting request at the next sync point.
         Returns the list of generated token lists, in request order.  logprobs: k for every request, or a list with one k / None per
-        request -> (token lists, entry lists) (entries as in generate_one; None for a request that did not ask)."""
+        request -> (token lists, entry lists) (entries as in generate_one; None for a request that did not ask).
+        controls: None = the slots keep their logit controls (set_sampling / set_slot_controls); a dict of repetition_penalty /
+        frequency_penalty / presence_penalty / min_p for every request, or a list with one dict / None (= the defaults) per request."""
+        ctl = None if controls is None else self._request_controls(controls, len(requests))
         ks = list(logprobs) if isinstance(logprobs, (list, tuple)) else [logprobs] * len(requests)
         if len(ks) != len(requests):
             raise ValueError("logprobs: one value per request")
@@ -1336,7 +1458,8 @@ class ChatTSForCausalLM:
         if want:
             self.set_logprobs(True)
         if self.max_batch < 2:
-            outs = [self.generate_one(i, s, l, max_new_tokens, eos_token_id, logprobs=k) for (i, s, l), k in zip(requests, ks)]
+            outs = [self.generate_one(i, s, l, max_new_tokens, eos_token_id, logprobs=k, controls=None if ctl is None else (ctl[j] or {}))
+                    for j, ((i, s, l), k) in enumerate(zip(requests, ks))]
             if logprobs is None:
                 return outs
             return [o[0] if k is not None else o for o, k in zip(outs, ks)], [o[1] if k is not None else None for o, k in zip(outs, ks)]
@@ -1381,6 +1504,8 @@ class ChatTSForCausalLM:
                         ids, series, lengths = requests[r]
                         s = self.pick_slot(free, self._request_idents(ids, series, lengths))
                         free.remove(s)
+                        if ctl is not None:
+                            self.set_slot_controls(s, **(ctl[r] or {}))
                         items.append((s, ids, series, lengths, max_new_tokens))
                         members.append((s, r))
                     try:
@@ -1400,6 +1525,8 @@ class ChatTSForCausalLM:
                         raise KvPoolExhausted(f"request {waiting[-1]} needs more KV blocks than the pool holds ({self.kv_stats()})")
                     break                                    # wait until a running sequence finishes and its blocks become evictable
                 s = self.pick_slot(free, self._request_idents(ids, series, lengths))
+                if ctl is not None:
+                    self.set_slot_controls(s, **(ctl[waiting[-1]] or {}))
                 try:
                     self._admit(s, ids, series, lengths, max_new_tokens)
                 except RuntimeError as e:                    # (the reservation is _admit's first change: nothing to undo)
@@ -1444,10 +1571,13 @@ class ChatTSForCausalLM:
 
     @torch.no_grad()
     def generate_one(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, sync_every=16,
-                     return_logits=False, logprobs=None):
+                     return_logits=False, logprobs=None, controls=None):
         """ids: un-expanded prompt ids (host list); series: [n, 2*Lmax, 1] tensor of this prompt's series.
         logprobs=k (0 <= k <= max_logprobs): also return one (logprob, rank, top-k [(id, logprob)]) entry per returned token, last in
-        the result tuple (toks[, logits0], entries)."""
+        the result tuple (toks[, logits0], entries).  controls: None = slot 0 keeps its logit controls; a dict of repetition_penalty /
+        frequency_penalty / presence_penalty / min_p (missing = default) sets them for this request."""
+        if controls is not None:
+            self.set_slot_controls(0, **controls)
         if logprobs is not None:
             self._check_logprobs(logprobs)
             self.set_logprobs(True)
@@ -1480,10 +1610,12 @@ class ChatTSForCausalLM:
             raise ValueError(f"logprobs={k!r} must be an integer in 0..max_logprobs={self.max_logprobs}")
 
     @torch.no_grad()
-    def generate_stream(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, chunk=1):
+    def generate_stream(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, chunk=1, controls=None):
         """Generator over the new tokens of ONE request: yields a list of token ids every `chunk` decode steps (chunk=1: token by
         token, what an SSE stream / HF TextStreamer consumes; each yield costs one device->host read of the tokens so far).
-        Stops after an EOS token (which is yielded) or max_new_tokens.  Same kernels and tokens as generate_one."""
+        Stops after an EOS token (which is yielded) or max_new_tokens.  Same kernels and tokens as generate_one (controls too)."""
+        if controls is not None:
+            self.set_slot_controls(0, **controls)
         eos = _eos_set(eos_token_id)
         self._prefill_request(ids, series, lengths, max_new_tokens)
         produced, sent = 1, 0
@@ -1505,6 +1637,7 @@ class ChatTSForCausalLM:
     def _prefill_request(self, ids, series, lengths, max_new_tokens):
         """TS encode + merge + prefill + first token of one request on the single-sequence path -> prompt length T."""
         T, emb, idents, _, _ = self._prepare_request(ids, series, lengths, max_new_tokens)
+        self._controls_admit(0, ids)
         self.reserve_kv(0, T + max_new_tokens, idents)
         n0 = self._reuse_prefix(0, idents, T)
         self._slot_idents[0] = idents
@@ -1518,17 +1651,19 @@ class ChatTSForCausalLM:
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, timeseries=None, max_new_tokens=64, max_length=None,
                  streamer=None, eos_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None,
-                 seed=0, synced_gpus=False, valid_lengths=None, **kw):
+                 seed=0, synced_gpus=False, valid_lengths=None, repetition_penalty=None, min_p=None, **kw):
         """model.generate(**inputs, max_new_tokens=...) -> LongTensor [B, T_in + new] (README.md:102, demo_hf.ipynb
         cell 5).  Greedy unless do_sample=True, like HF; with do_sample the HF GenerationConfig defaults apply to what is
         not given (temperature 1.0, top_k 50, top_p 1.0; the reference's deepspeed driver passes temperature=0.2,
         inference_tsmllm_deepspeed.py:95-100).  Rows start with the un-expanded input_ids; shorter rows are
-        right-padded with pad_token_id.  A flat `timeseries` tensor is consumed across the batch in prompt order."""
+        right-padded with pad_token_id.  A flat `timeseries` tensor is consumed across the batch in prompt order.
+        repetition_penalty and min_p have HF's meaning: the penalty applies with and without do_sample, min_p only with it."""
         if do_sample:
             self.set_sampling(1.0 if temperature is None else temperature, 50 if top_k is None else top_k,
-                              1.0 if top_p is None else top_p, seed)
+                              1.0 if top_p is None else top_p, seed, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
+                              min_p=min_p)
         else:
-            self.set_sampling(0.0)
+            self.set_sampling(0.0, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty)
         cfg = self.config
         ids = input_ids if isinstance(input_ids, torch.Tensor) else torch.tensor(input_ids)
         if ids.dim() == 1:

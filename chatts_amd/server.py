@@ -82,6 +82,14 @@ def sampling_from_body(body, default_max_tokens=512):
         out = dict(max_tokens=int(mt), temperature=0.0 if temp is None else float(temp), top_p=1.0 if top_p is None else float(top_p),
                    top_k=int(body.get("top_k") or 0), seed=None if body.get("seed") is None else int(body["seed"]),
                    stop_token_ids=[int(t) for t in (body.get("stop_token_ids") or [])], ignore_eos=bool(body.get("ignore_eos", False)))
+        # presence_penalty / frequency_penalty (OpenAI) and repetition_penalty / min_p (vLLM's extra fields): kept only when sent, so an
+        # engine without them never sees the keywords
+        for name in ("presence_penalty", "frequency_penalty", "repetition_penalty", "min_p"):
+            v = body.get(name)
+            if v is not None:
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ValueError(f"{name} must be a number, got {v!r}")
+                out[name] = float(v)
     except (TypeError, ValueError) as e:
         raise ValueError(f"malformed sampling parameter: {e}")
     from .engine import validate_sampling

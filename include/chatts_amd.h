@@ -497,6 +497,47 @@ int chatts_logprobs_batched(const float* logits, int batch, int64_t logits_strid
                             int32_t* out_top_ids, float* out_top_lp, void* workspace, size_t workspace_bytes,
                             chatts_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Logit controls: repetition / presence / frequency penalties and min_p, with vLLM's names and meaning, applied to the logits of a
+ * step BEFORE the selection (vLLM V1's sampler order: raw logits -> repetition -> frequency and presence -> [greedy rows: argmax of
+ * these] -> temperature -> min_p -> top-k -> top-p -> draw).  With c = how often the id occurs among the tokens GENERATED so far:
+ *   repetition r: every id that occurs in the prompt or has c > 0:  l = l / r if l > 0 else l * r
+ *   frequency f, presence p:  l -= f * c;  l -= p if c > 0
+ *   min_p (rows with temperature T > 0 only): with m the row maximum of the penalised logits, id i survives iff
+ *           l_i >= m + T * log(min_p) (its probability after temperature is >= min_p times the largest); the others become -inf, so the
+ *           sampler's top-k / top-p run over the survivors.  Ties at the cut are kept.  min_p == 0 or T == 0: inert.
+ * The raw logits are only read; the result goes to args.out (another buffer), which is what the selection is then given: logprobs stay
+ * log_softmax of the RAW logits, and the selection's token_logit is the penalised logit.
+ * State: int32 [rows, state_stride], cell j of a row <-> global id vocab_offset + j: bit 30 = "in the prompt", bits 0..29 = c
+ * (saturating).  An id whose cell is 0 keeps its logit bit for bit; so does every id of a row with r = 1, f = p = 0, min_p = 0.
+ * Row b of every array of the struct belongs to row b of the logits.  Per-row parameters are device arrays read at run time (NULL =
+ * that control is off for every row), so a captured decode step serves requests with different settings.  Fixed reduction shapes, no
+ * float atomics: the same logits and state give the same bits.  vocab <= 2^31 - 1 - vocab_offset.
+ *   chatts_logit_controls_apply  two launches (penalties + slice maxima; min_p cut - skipped when min_p_rows or temperature_rows is
+ *                                NULL), >= chatts_logit_controls_workspace(batch) bytes of device scratch; graph-capturable
+ *   chatts_logit_state_reset     one sequence's row: cleared, then the ids of prompt_ids[0 .. n_prompt) (device, global ids; those outside
+ *                                the slice are skipped) are marked "in the prompt"
+ *   chatts_logit_state_update    row b: the count of token[b] += 1 (tokens outside the slice are skipped); graph-capturable
+ * ------------------------------------------------------------------------------------------- */
+typedef struct ChattsLogitControlArgs {
+  int32_t* state;                 /* [rows, state_stride] */
+  int64_t state_stride;           /* >= vocab */
+  float* out;                     /* [rows, out_stride] penalised logits */
+  int64_t out_stride;             /* >= vocab */
+  const float* repetition_rows;   /* [rows] r > 0; NULL = 1 */
+  const float* frequency_rows;    /* [rows] f; NULL = 0 */
+  const float* presence_rows;     /* [rows] p; NULL = 0 */
+  const float* min_p_rows;        /* [rows] in [0, 1]; NULL = 0 */
+  const float* temperature_rows;  /* [rows] the T the row is sampled with (0 = greedy), for the min_p cut; NULL = min_p is off */
+} ChattsLogitControlArgs;
+size_t chatts_logit_controls_workspace(int batch);
+int chatts_logit_controls_apply(const float* logits, int batch, int64_t logits_stride, int64_t vocab, int64_t vocab_offset,
+                                const ChattsLogitControlArgs* args, void* workspace, size_t workspace_bytes, chatts_stream_t stream);
+int chatts_logit_state_reset(int32_t* state_row, int64_t vocab, int64_t vocab_offset, const int64_t* prompt_ids, int64_t n_prompt,
+                             chatts_stream_t stream);
+int chatts_logit_state_update(int32_t* state, int64_t state_stride, int batch, int64_t vocab, int64_t vocab_offset,
+                              const int64_t* token, chatts_stream_t stream);
+
 /* x[h] = float(table[*token - vocab_offset, h]) : next-step input embedding, token id read on the device. */
 int chatts_embed_token(const int64_t* token_dev, const chatts_bf16* table, int64_t vocab_offset,
                        int64_t vocab_rows, int hidden, float* out, chatts_stream_t stream);
@@ -741,6 +782,20 @@ int chatts_decoder_select_tokens(ChattsDecoder*, const float* logits, int batch,
 int chatts_decoder_logprobs(ChattsDecoder*, const float* logits, int batch, int64_t logits_stride, int k, const int64_t* token,
                             const int32_t* step_dev, int64_t out_stride, float* out_lp, int32_t* out_rank, int32_t* out_top_ids,
                             float* out_top_lp, chatts_stream_t stream);
+
+/* Logit controls of every selection of this decoder (chatts_decoder_select_tokens and the decode steps, whose row b is cache slot b):
+ * NULL (default) = off, the selection is exactly what it is without the feature.  Otherwise (copied) every selection runs
+ * chatts_logit_controls_apply on the decoder's idle workspace, selects from args.out, and then chatts_logit_state_update with the
+ * chosen tokens.  Under tensor parallelism the logits are first gathered into buffers.logits_full (chatts_allgather) and every rank runs
+ * the pass and the selection on the full vocabulary (state and out rows of vocab_local * tp_world cells, offset 0): identical tokens on
+ * every rank, equal to the TP = 1 token for the same logits.  Changing it invalidates any hipGraph captured over a decode step. */
+int chatts_decoder_set_logit_controls(ChattsDecoder*, const ChattsLogitControlArgs* args_or_null);
+/* chatts_decoder_select_tokens with the logit controls of THIS call (row b of `controls` <-> row b of the logits: a request admitted
+ * into cache slot s passes the arrays advanced by s); NULL = the decoder's own setting, i.e. chatts_decoder_select_tokens itself. */
+int chatts_decoder_select_tokens_controlled(ChattsDecoder*, const float* logits, int batch, int64_t logits_stride, int64_t* token,
+                                            float* token_logit, int64_t* out_tokens, int64_t out_stride, int32_t* step_dev,
+                                            int32_t* pos_dev, int pos_limit, const ChattsSamplingArgs* override_or_null,
+                                            const ChattsLogitControlArgs* controls_or_null, chatts_stream_t stream);
 
 /* Token selection of chatts_decoder_decode_step(_batched): NULL (default) = greedy argmax; otherwise the sampler above
  * with these parameters (copied).  Changing it invalidates any hipGraph captured over a decode step. */
