@@ -30,6 +30,7 @@ class TsWeights(C.Structure):
 
 
 LOGPROBS_MAX_K = 64       # CHATTS_LOGPROBS_MAX_K of include/chatts_amd.h
+FORK_MAX_DST = 64         # CHATTS_FORK_MAX_DST: destinations of one chatts_kv_fork / chatts_logit_state_fork call
 ABI_VERSION = 9            # CHATTS_ABI_VERSION of include/chatts_amd.h this binding was written against (checked by load())
 W8_FP8, W8_INT8 = 0, 1     # ChattsLinearArgs.w8_format
 
@@ -219,6 +220,10 @@ SIGNATURES = {
                                             c_void_p]),
     "chatts_logit_state_reset": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "chatts_logit_state_update": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    # fork for parallel sampling (kv_fork.hip)
+    "chatts_kv_fork": (c_int, [C.POINTER(KvCache), c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, C.POINTER(c_int32), c_int,
+                               c_int, c_int, c_void_p]),
+    "chatts_logit_state_fork": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, C.POINTER(c_int32), c_int, c_void_p]),
     # tensor-parallel exchange (tp.hip)
     "chatts_tp_buffer_bytes": (c_size_t, [c_int, c_int64]),
     "chatts_tp_buffer_bytes_bulk": (c_size_t, [c_int, c_int64, c_int64]),

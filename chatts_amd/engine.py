@@ -44,13 +44,30 @@ def validate_controls(repetition_penalty=None, frequency_penalty=None, presence_
 NO_CONTROLS = (1.0, 0.0, 0.0, 0.0)
 
 
+def validate_n(n=None, best_of=None, max_num_seqs=None):
+    """n (samples per prompt, vLLM's name) -> int >= 1; best_of only as None or equal to n (vLLM V1 removed it); siblings are admitted
+    together, so n may not exceed max_num_seqs (checked when given).  ValueError otherwise."""
+    n = 1 if n is None else n
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    if best_of is not None and (isinstance(best_of, bool) or not isinstance(best_of, (int, np.integer)) or int(best_of) != int(n)):
+        raise ValueError(f"best_of is accepted only as None or equal to n={n}, got {best_of!r}")
+    if max_num_seqs is not None and int(n) > int(max_num_seqs):
+        raise ValueError(f"n={n} exceeds max_num_seqs={max_num_seqs}: the samples of one prompt are admitted together")
+    return int(n)
+
+
 def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, logprobs=None, max_logprobs=20, prompt_logprobs=None,
-                      repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None, **_):
+                      repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None, n=None, best_of=None,
+                      stop=None, **_):
     """The ranges vLLM's SamplingParams accepts (what the reference's drivers pass: inference_tsmllm_vllm.py:43-46,
     llm_utils.py:153).  Raises ValueError - the server turns it into a 400 - BEFORE the request can reach the engine thread, where
     an out-of-range value would otherwise surface inside set_sampling / chatts_decoder_set_sampling."""
     import math
+    from .detok import normalize_stop
     validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
+    validate_n(n, best_of)
+    normalize_stop(stop)
     t = 0.0 if temperature is None else float(temperature)
     if not math.isfinite(t) or t < 0.0:
         raise ValueError(f"temperature must be a finite number >= 0, got {temperature}")
@@ -86,6 +103,18 @@ class Request:
         self.error = None
         self.controls = NO_CONTROLS          # (repetition_penalty, frequency_penalty, presence_penalty, min_p): Engine.add_request
         self.bypassed = 0                    # later arrivals admitted past this request while it waited for its sampling group
+        # n > 1 (parallel sampling): the request the caller holds is the PARENT - it never occupies a slot; `children` are the n
+        # sequences (index 0 .. n-1, each with the fields of a request of its own), `remaining` those still running
+        self.n, self.index, self.parent, self.children, self.remaining = 1, 0, None, None, 0
+        # stop strings: `text` is then the engine's own decode (what a stream may show so far; the final text once finished)
+        self.stop, self.include_stop, self.checker, self.text = [], False, None, None
+        self.stop_reason = None              # the matched stop string, the id of a stop_token_ids hit, None for EOS / length
+        self.stop_ids = set()
+
+    @property
+    def outputs(self):
+        """the n sequences of this request in index order (the request itself when n == 1)"""
+        return list(self.children) if self.children else [self]
 
 
 class Engine:
@@ -121,11 +150,16 @@ class Engine:
     # ---- requests ---------------------------------------------------------------------------------
     def add_request(self, prompt, timeseries=None, max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, seed=None,
                     stop_token_ids=None, ignore_eos=False, on_tokens=None, logprobs=None, repetition_penalty=None,
-                    frequency_penalty=None, presence_penalty=None, min_p=None):
+                    frequency_penalty=None, presence_penalty=None, min_p=None, n=1, best_of=None, stop=None,
+                    include_stop_str_in_output=False):
         """seed None: per-slot mode gives every request its own stream (a hash of its arrival number - vLLM's seed=None means "not
         reproducible across requests"; here two identical prompts still differ, and a rerun of the same arrival order repeats);
-        grouped mode uses 0 (requests that decode together must share ONE configuration there)."""
+        grouped mode uses 0 (requests that decode together must share ONE configuration there).
+        n > 1: -> the parent request; its `children` are n sequences of the one prompt, child i drawing with seed + i (mod 2^32), all
+        admitted together from ONE prefill (step()).  on_tokens is called per child (`r.index`, `r.parent`).
+        stop: strings that end a sequence when they appear in its decoded text (chatts_amd/detok.py: the rule)."""
         validate_sampling(max_tokens, temperature, top_p, top_k, logprobs=logprobs, max_logprobs=self.max_logprobs)
+        n, stop = self.check_request(n, best_of, stop)
         controls = validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
         if controls != NO_CONTROLS and not hasattr(self.model, "set_slot_controls"):
             raise ValueError("this model does not apply repetition / frequency / presence penalties or min_p")
@@ -145,8 +179,34 @@ class Engine:
             r.logprob_k, r.logprobs, r.cumulative_logprob = int(logprobs), [], 0.0
         if self.mixed:
             r.sampling_key = "rows" if key is not None else None     # one group: who samples is a per-slot matter
+        r.stop, r.include_stop, r.stop_ids = stop, bool(include_stop_str_in_output), {int(t) for t in (stop_token_ids or [])}
+        if n > 1:
+            r.n, r.remaining, r.children = n, n, []
+            for i in range(n):
+                c = Request(r.rid, prompt, r.timeseries, max_tokens, r.sampling_key, eos, on_tokens)
+                c.index, c.parent, c.controls, c.t_arrival = i, r, controls, r.t_arrival
+                c.sampling = r.sampling[:3] + ((int(seed) + i) & 0xFFFFFFFF,)
+                c.stop, c.include_stop, c.stop_ids = stop, r.include_stop, r.stop_ids
+                if logprobs is not None:
+                    c.logprob_k, c.logprobs, c.cumulative_logprob = int(logprobs), [], 0.0
+                r.children.append(c)
         self.waiting.append(r)
         return r
+
+    def check_request(self, n=None, best_of=None, stop=None, **_):
+        """What this engine refuses about n and stop beyond their value ranges (ValueError): n > max_num_seqs, n > 1 on a model without
+        per-slot sampling settings or without a fork, stop strings without a tokenizer.  -> (n, list of stop strings).  add_request
+        calls it; EngineThread calls it BEFORE a request is announced to the follower ranks."""
+        from .detok import normalize_stop
+        n = validate_n(n, best_of, self.nslots)
+        stop = normalize_stop(stop)
+        if n > 1 and not self.mixed:
+            raise ValueError("n > 1 needs a model with per-slot sampling settings (set_slot_sampling)")
+        if n > 1 and not hasattr(self.model, "admit_fork"):
+            raise ValueError("this model cannot fork a prompt into several samples (n > 1)")
+        if stop and getattr(self.processor, "tokenizer", None) is None:
+            raise ValueError("stop strings need a tokenizer (the engine's processor has none)")
+        return n, stop
 
     @property
     def max_logprobs(self):
@@ -236,6 +296,72 @@ class Engine:
         if r.on_tokens is not None and (new or finished):
             r.on_tokens(r, new, finished)
 
+    def _fail(self, r, e, done):
+        r.error = e
+        for c in (r.children or ()):
+            c.error, c.finished, c.finish_reason = e, True, "error"
+        self._emit(r, True, "error")
+        done.append(r)
+
+    def _place(self, r, s, st=None):
+        """the admission of r into slot s is complete: it runs from now on (n > 1: its children, in s and the forked slots)"""
+        if r.n > 1:
+            for c, sl in zip(r.children, [s] + list(st["fork"])):
+                c.prompt_tokens = r.prompt_tokens
+                self.slots[sl], self.produced[sl] = c, 1
+        else:
+            self.slots[s], self.produced[s] = r, 1
+
+    def _admit_parent(self, r, free, done):
+        """Admission of a request with n > 1 (the head of the queue; n slots are free): ONE preparation and ONE prefill into the slot
+        child 0 takes, the other n - 1 slots are forked from it (model.admit_fork / admit_step).  -> "ok", "failed" (the request was
+        answered with an error) or "wait" (the block pool cannot hold it yet, or its prompt is now being prefilled in chunks)."""
+        m = self.model
+        if getattr(r, "_enc", None) is None:
+            try:
+                r._enc = self._encode(r)
+                r.prompt_tokens = len(r._enc[0])
+            except Exception as e:
+                self.waiting.remove(r)
+                self._fail(r, e, done)
+                return "failed"
+        ids, ser, lens = r._enc
+        if getattr(m, "_kv_dynamic", False):
+            T = m.request_tokens(ids, ser, lens)
+            need = [T + r.max_tokens] + [m.fork_tokens(T, r.max_tokens)] * (r.n - 1)      # shared prompt blocks counted once
+            if not m.kv_fits(need):
+                if any(v is not None for v in self.slots):
+                    return "wait"
+                self.waiting.remove(r)
+                self._fail(r, RuntimeError(f"request needs {sum(need)} KV positions for its {r.n} samples, more than the block pool "
+                                           f"can hold ({m.kv_stats()})"), done)
+                return "failed"
+        s = m.pick_slot(list(free), m._request_idents(ids, ser, lens)) if hasattr(m, "pick_slot") else free[0]
+        kids = [f for f in free if f != s][:r.n - 1]
+        self.waiting.remove(r)
+        for c, sl in zip(r.children, [s] + kids):        # every sibling's own settings, before its first token is drawn
+            m.set_slot_sampling(sl, *c.sampling)
+            if hasattr(m, "set_slot_controls"):
+                m.set_slot_controls(sl, *c.controls)
+        try:
+            st = m.admit_fork(m.admit_begin(s, ids, ser, lens, r.max_tokens), kids, r.max_tokens)
+            if (self.prefill_chunk_tokens and any(v is not None for v in self.slots)
+                    and st["T"] - st["done"] > self.prefill_chunk_tokens):
+                self.prefilling = (r, s, st)             # others are decoding: the one prefill goes in chunks between their steps
+                m.admit_step(st, self.prefill_chunk_tokens)
+                return "wait"
+            m.admit_step(st)
+        except Exception as e:
+            self.prefilling = None
+            if type(e).__name__ == "KvPoolExhausted" and any(v is not None for v in self.slots):
+                self.waiting.appendleft(r)
+                return "wait"
+            self._fail(r, e, done)
+            return "failed"
+        self._place(r, s, st)
+        self._since_sync = self.sync_every               # read the first tokens right away
+        return "ok"
+
     # ---- one scheduler iteration ---------------------------------------------------------------------
     def step(self):
         """Admit what fits, advance every running sequence by one token, deliver finished / newly read tokens.
@@ -261,13 +387,11 @@ class Engine:
             try:
                 if m.admit_step(st, self.prefill_chunk_tokens):
                     self.prefilling = None
-                    self.slots[s], self.produced[s] = r, 1
+                    self._place(r, s, st)
                     self._since_sync = self.sync_every   # read the first token right away
             except Exception as e:
                 self.prefilling = None
-                r.error = e
-                self._emit(r, True, "error")
-                done.append(r)
+                self._fail(r, e, done)
         # admission: free slots take waiting requests that share the running batch's sampling configuration
         while self.prefilling is None and self.waiting and any(v is None for v in self.slots):
             free = [i for i, v in enumerate(self.slots) if v is None]
@@ -275,8 +399,26 @@ class Engine:
             # one (it joins when the batch has drained) - but only `max_bypass` times, or a steady stream of same-key arrivals
             # would starve it
             head = self.waiting[0]
+            if head.n > 1:                               # n samples of one prompt: admitted together, from one prefill
+                if head.n <= len(free):
+                    if self._admit_parent(head, free, done) == "wait":
+                        break
+                    continue
+                if head.bypassed >= self.max_bypass:     # it waits for n free slots; later single requests may pass it, a few times
+                    break
             if self.mixed:
-                cands = list(self.waiting)[:len(free)]
+                cands = []
+                for q in self.waiting:                   # arrival order; a later request with n > 1 ends the run (it goes first then)
+                    if q.n > 1:
+                        if q is head:
+                            continue
+                        break
+                    cands.append(q)
+                cands = cands[:len(free)]
+                if not cands:
+                    break
+                if head.n > 1:
+                    head.bypassed += len(cands)
             else:
                 if head.sampling_key != self.active_key and head.bypassed >= self.max_bypass:
                     break
@@ -408,8 +550,14 @@ class Engine:
             cut = next((i + 1 for i, t in enumerate(toks) if t in r.eos), None) if r.eos else None
             if r.t_first is None:
                 r.t_first = time.perf_counter()
+                if r.parent is not None and r.parent.t_first is None:
+                    r.parent.t_first = r.t_first
+            if r.stop and self._check_stop(s, r, toks, cut, done):
+                continue
             if cut is not None:
                 r.tokens = toks[:cut]
+                if r.tokens[-1] in r.stop_ids:
+                    r.stop_reason = r.tokens[-1]
                 self._read_logprobs(s, r)
                 self._retire(s, "stop", done)
             elif self.produced[s] >= r.max_tokens:
@@ -421,6 +569,27 @@ class Engine:
                 self._read_logprobs(s, r)
                 self._emit(r, False)
         return done
+
+    def _check_stop(self, s, r, toks, cut, done):
+        """Stop strings of the sequence in slot s over the tokens this harvest read, in generation order: only the tokens before an
+        EOS / stop token or the max_tokens limit can match (a sequence ends at the smallest j).  -> True when the sequence was retired
+        here (a stop string matched: the tokens generated past the match are dropped); otherwise r.text is what a stream may show."""
+        from .detok import StopChecker
+        if r.checker is None:
+            r.checker = StopChecker(self.processor.tokenizer, r.stop, r.include_stop)
+        limit = min(len(toks), r.max_tokens) if cut is None else cut
+        seen = len(r.checker.ids)
+        hit = r.checker.push(toks[seen:limit])
+        if hit is not None and not (cut is not None and hit[0] == cut):      # (at the same j the EOS / stop token ends it)
+            r.tokens, r.text, r.stop_reason = toks[:hit[0]], hit[1], hit[2]
+            self._read_logprobs(s, r)
+            self._retire(s, "stop", done)
+            return True
+        if cut is not None or self.produced[s] >= r.max_tokens:
+            r.text = r.checker.finish(toks[:limit])
+        else:
+            r.text = r.checker.released
+        return False
 
     def _read_logprobs(self, s, r):
         """the entries of the tokens read in this harvest (requests that asked only)"""
@@ -437,7 +606,14 @@ class Engine:
             self.model.buf["pos_all"][s] = -1         # parked: the batched step neither attends nor writes this slot's cache
         self.model.note_generated(s, r.tokens)
         self._emit(r, True, reason)
-        done.append(r)
+        p = r.parent
+        if p is None:
+            done.append(r)
+            return
+        p.remaining -= 1                              # a sibling: its slot is free now; the parent completes with the last one
+        if p.remaining == 0:
+            p.finished, p.finish_reason = True, reason
+            done.append(p)
 
     def run_until_done(self):
         out = []
@@ -566,8 +742,10 @@ class EngineThread:
         for kw in new:
             try:
                 validate_sampling(**{k: kw[k] for k in ("max_tokens", "temperature", "top_p", "top_k", "logprobs", "repetition_penalty",
-                                                          "frequency_penalty", "presence_penalty", "min_p") if k in kw},
-                                  max_logprobs=getattr(self.engine, "max_logprobs", 20))
+                                                          "frequency_penalty", "presence_penalty", "min_p", "n", "best_of", "stop")
+                                     if k in kw}, max_logprobs=getattr(self.engine, "max_logprobs", 20))
+                if hasattr(self.engine, "check_request"):       # n > slots, n > 1 / stop on an engine that cannot serve them
+                    self.engine.check_request(kw.get("n"), kw.get("best_of"), kw.get("stop"))
                 ok.append(kw)
             except (ValueError, TypeError) as e:
                 r = Request(-1, kw.get("prompt"), list(kw.get("timeseries") or []), 1, None, [], kw.get("on_tokens"))

@@ -146,8 +146,9 @@ class LLMClient:
                  qwen_template=True, **llm_kw):
         if engine not in ("vllm-ts", "dryrun"):
             raise NotImplementedError(f"Unrecognized inference engine: {engine}")
-        if sample_n != 1:
-            raise NotImplementedError("sample_n > 1 (several samples per prompt) is not served by this engine")
+        if isinstance(sample_n, bool) or not isinstance(sample_n, int) or sample_n < 1:
+            raise ValueError(f"sample_n must be an integer >= 1, got {sample_n!r}")
+        self.sample_n = sample_n                 # > 1: answers are lists of sample_n texts (llm_utils.py:178-182), SamplingParams.n
         if chat_template is not None:
             raise NotImplementedError("custom jinja chat templates are not rendered here: pass ready prompts with use_chat_template=False")
         self.engine, self.system_prompt, self.batch_size = engine, system_prompt, int(batch_size)
@@ -168,11 +169,12 @@ class LLMClient:
     def default_sampling_params(self):
         """the worker's own default (llm_utils.py:153): temperature 0.5, top_p 0.95, stop at <|endoftext|> / <|im_end|>"""
         from .llm import SamplingParams
-        return SamplingParams(temperature=0.5, top_p=0.95, max_tokens=512, stop_token_ids=[151643, 151645])
+        extra = {"n": self.sample_n} if self.sample_n > 1 else {}
+        return SamplingParams(temperature=0.5, top_p=0.95, max_tokens=512, stop_token_ids=[151643, 151645], **extra)
 
     def llm_batch_generate(self, batch_prompts, batch_timeseries=None, dryrun_outputs=None, use_chat_template=True,
                            sampling_params=None):
-        """-> one answer string per prompt, in prompt order; None for the prompts another replica owns (llm_utils.py:330-336
+        """-> one answer string per prompt (sample_n > 1: a list of sample_n strings), in prompt order; None for the prompts another replica owns (llm_utils.py:330-336
         returns None for unanswered positions)."""
         if batch_timeseries is not None and len(batch_prompts) != len(batch_timeseries):
             raise AssertionError(f"len(batch_prompts) != len(batch_timeseries): {len(batch_prompts)} != {len(batch_timeseries)}")
@@ -195,7 +197,7 @@ class LLMClient:
                 else:
                     reqs.append({"prompt": text})
             for i, out in zip(idxs, self.llm.generate(reqs, sp, use_tqdm=False)):
-                answers[i] = out.outputs[0].text
+                answers[i] = [o.text for o in out.outputs] if self.sample_n > 1 else out.outputs[0].text
         return answers
 
     def kill(self):

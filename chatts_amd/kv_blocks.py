@@ -129,6 +129,19 @@ class BlockPool:
             changed = True
         return changed
 
+    def fork(self, slot, src, n_blocks):
+        """Parallel sampling: `slot` becomes a sibling of `src`, whose prompt has just been prefilled.  src's first n_blocks blocks (the
+        whole prompt blocks: shared, reference counted) go IN FRONT of the private blocks `slot` reserved beforehand for everything
+        from the trailing prompt block on, so the block both write next is private to each.  (Sharing only after the prefill: a
+        slot never writes a shared block, so src's prefill would swap blocks it shared earlier for private ones.)"""
+        if slot == src or n_blocks > len(self.rows[src]) or n_blocks + len(self.rows[slot]) > self.blocks_per_slot:
+            raise ValueError("fork: the source row is shorter than the shared prefix, or the destination's row would outgrow its table")
+        if set(self.rows[src][:n_blocks]) & set(self.rows[slot]):
+            raise ValueError("fork: the destination already holds a block of the shared prefix")
+        for b in self.rows[src][:n_blocks]:
+            self.refs[b] += 1
+        self.rows[slot] = list(self.rows[src][:n_blocks]) + self.rows[slot]
+
     def retire(self, slot):
         """the slot's request finished: its blocks stay (prefix reuse) but may be evicted from now on"""
         self.active.discard(slot)

@@ -12,8 +12,19 @@ import numpy as np
 class SamplingParams:
     def __init__(self, max_tokens=16, temperature=0.0, top_p=1.0, top_k=-1, seed=None, stop_token_ids=None,
                  ignore_eos=False, logprobs=None, prompt_logprobs=None, repetition_penalty=1.0, frequency_penalty=0.0,
-                 presence_penalty=0.0, min_p=0.0, **kw):
-        from .engine import validate_controls
+                 presence_penalty=0.0, min_p=0.0, n=1, best_of=None, stop=None, include_stop_str_in_output=False, **kw):
+        from .detok import normalize_stop
+        from .engine import validate_controls, validate_n
+        # n: samples per prompt (RequestOutput.outputs[i], i = 0 .. n-1).  Sample i draws with seed + i from a stream of (seed, step)
+        # alone, so it is what an Engine / server request with seed + i generates, and sample 0 is that surface's n = 1 answer.
+        # (LLM.generate serves n = 1 without stop through generate_batch's shared configuration, which with max_num_seqs > 1 folds
+        # the cache slot into the draws: there a sampled n = 1 call is not sample 0 of the n = 2 call - LLM._generate_engine.)
+        # best_of only as None or n.  stop: strings that end a sequence where they appear in its decoded text - the text ends before
+        # the match, or after it with include_stop_str_in_output (chatts_amd/detok.py: the rule)
+        self.n = validate_n(n, best_of)
+        self.best_of = best_of
+        self.stop = normalize_stop(stop)
+        self.include_stop_str_in_output = bool(include_stop_str_in_output)
         if prompt_logprobs is not None:
             raise ValueError("prompt_logprobs is not supported (only the logprobs of generated tokens: logprobs=k)")
         if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or logprobs < 0):
@@ -43,8 +54,11 @@ class Logprob:
 
 
 class CompletionOutput:
-    def __init__(self, text, token_ids, logprobs=None, cumulative_logprob=None):
-        self.text, self.token_ids, self.index = text, token_ids, 0
+    def __init__(self, text, token_ids, logprobs=None, cumulative_logprob=None, index=0, finish_reason=None, stop_reason=None):
+        self.text, self.token_ids, self.index = text, token_ids, index
+        # finish_reason: "stop" (EOS, a stop token, a stop string) / "length"; stop_reason: the matched stop string, the id of a
+        # stop_token_ids hit, None otherwise (vLLM's convention)
+        self.finish_reason, self.stop_reason = finish_reason, stop_reason
         # logprobs: one {token_id: Logprob} per generated token (its top-k + the chosen token); None when not requested
         self.logprobs, self.cumulative_logprob = logprobs, cumulative_logprob
 
@@ -160,6 +174,8 @@ class LLM:
         sp = sampling_params or SamplingParams()
         if sp.logprobs is not None and sp.logprobs > self.model.max_logprobs:
             raise ValueError(f"logprobs={sp.logprobs} exceeds max_logprobs={self.model.max_logprobs} (LLM(max_logprobs=...))")
+        if getattr(sp, "n", 1) > 1 or getattr(sp, "stop", None):
+            return self._generate_engine(prompts, sp)         # per-slot seeds / stop strings: through an Engine on this model
         self.model.set_logprobs(sp.logprobs is not None)      # per call, like the sampling mode (a switch re-captures the graphs)
         controls = (sp.repetition_penalty, sp.frequency_penalty, sp.presence_penalty, sp.min_p)
         if controls == (1.0, 0.0, 0.0, 0.0):
@@ -192,3 +208,48 @@ class LLM:
         return [RequestOutput(p, ids, [CompletionOutput(tok.decode(t, skip_special_tokens=True), t, _logprob_dicts(tok, t, e),
                                                         float(sum(x[0] for x in e)))])
                 for (p, ids), t, e in zip(metas, toks_all, entries_all)]
+
+    def _generate_engine(self, prompts, sp):
+        """generate() for n > 1 and / or stop strings: the requests go through a chatts_amd.engine.Engine on this model (per-slot
+        sampling settings and seeds, one prefill + fork per prompt, the stop rule at every harvest).  Sample i of a prompt draws with
+        seed + i, seed = SamplingParams.seed or this LLM's, from the per-slot stream hash(seed, step).
+        The n = 1 / no-stop path is left exactly as it was, and it draws differently when max_num_seqs > 1: generate_batch's one shared
+        configuration hashes (seed, cache slot, step) and folds the slot into the first token's seed, so that requests sharing ONE seed
+        do not draw alike.  Hence on such an LLM a sampled call changes its tokens when n > 1 or stop is added (greedy calls do not,
+        and neither does any call with max_num_seqs = 1, where there is no slot to fold); Engine and server requests always use the
+        per-slot stream, for n = 1 too."""
+        from .engine import Engine, validate_n
+        m = self.model
+        validate_n(sp.n, sp.best_of, max(1, m.max_batch))
+        if isinstance(prompts, (str, dict)):
+            prompts = [prompts]
+        if getattr(m, "_sampling_key", None) not in (None, "rows"):
+            m.set_sampling(0.0)                    # the engine works with per-slot settings: leave the baked-in configuration
+        eng = Engine(m, self.processor, sync_every=8)
+        eng.active_key = getattr(m, "_sampling_key", None)
+        kw = dict(max_tokens=sp.max_tokens, temperature=sp.temperature or 0.0, top_p=sp.top_p, top_k=max(int(sp.top_k or 0), 0),
+                  seed=self._seed if sp.seed is None else sp.seed, stop_token_ids=sp.stop_token_ids, ignore_eos=sp.ignore_eos,
+                  logprobs=sp.logprobs, repetition_penalty=sp.repetition_penalty, frequency_penalty=sp.frequency_penalty,
+                  presence_penalty=sp.presence_penalty, min_p=sp.min_p, n=sp.n, stop=sp.stop,
+                  include_stop_str_in_output=sp.include_stop_str_in_output)
+        reqs = []
+        for req in prompts:
+            if isinstance(req, str):
+                req = {"prompt": req}
+            series = list((req.get("multi_modal_data") or {}).get("timeseries", []))
+            if len(series) > self.limit:
+                raise ValueError(f"At most {self.limit} timeseries may be provided in one prompt, got {len(series)}")
+            reqs.append(eng.add_request(req["prompt"], timeseries=series, **kw))
+        eng.run_until_done()
+        tok = self.processor.tokenizer
+        outs = []
+        for r in reqs:
+            if r.error is not None:
+                raise r.error
+            cs = []
+            for c in r.outputs:
+                text = c.text if c.stop and c.text is not None else tok.decode(c.tokens, skip_special_tokens=True)
+                lps = _logprob_dicts(tok, c.tokens, c.logprobs) if c.logprob_k is not None else None
+                cs.append(CompletionOutput(text, c.tokens, lps, c.cumulative_logprob, c.index, c.finish_reason, c.stop_reason))
+            outs.append(RequestOutput(r.prompt, list(r._enc[0]), cs))
+        return outs

@@ -1323,7 +1323,12 @@ class ChatTSForCausalLM:
         last = self.prefill(st["emb"][a:b], a, for_next_token=final)
         st["done"] = b
         if final:
-            self._first_token_into_slot(slot, last - 1, T)
+            if st.get("fork"):               # parallel sampling: every sibling's first token from this one logits row
+                self._first_tokens_forked(slot, last - 1, T, st["fork"])
+                for c in st["fork"]:
+                    self._slot_idents[c] = list(st["idents"])
+            else:
+                self._first_token_into_slot(slot, last - 1, T)
             self._slot_idents[slot] = st["idents"]
             st["emb"] = None
         self.select_sequence(0)
@@ -1337,8 +1342,12 @@ class ChatTSForCausalLM:
 
     def _first_token_into_slot(self, slot, row, T):
         """logits of x[row] -> first token of the sequence in cache slot `slot` (out_tokens_all[slot, 0]); position / step set."""
-        B, st = self.buf, _lib.stream_ptr()
-        _lib.check(self.lib.chatts_decoder_logits(self._decoder, row, st))
+        _lib.check(self.lib.chatts_decoder_logits(self._decoder, row, _lib.stream_ptr()))
+        self._select_first(slot, T)
+
+    def _select_first(self, slot, T):
+        """the logits buffer -> first token of the sequence in cache slot `slot`, whose prompt of T positions is in its cache"""
+        B = self.buf
         B["pos_all"][slot] = T
         B["step_all"][slot] = 0
         sa = getattr(self, "_sampling", None)
@@ -1349,6 +1358,87 @@ class ChatTSForCausalLM:
             sa1 = _lib.SamplingArgs(temperature=sa.temperature, top_k=sa.top_k, top_p=sa.top_p,
                                     seed=(sa.seed ^ (0x51ED27 * (slot + 1))) & 0xFFFFFFFF, n_kept=None, kept_mass=None)
         self._select_one(slot, B["out_tokens_all"].shape[1], sa1)
+
+    # ---- fork: n samples of one prompt from ONE prefill (csrc/kv_fork.hip) ------------------------------------------------
+    def fork_tokens(self, T, max_new_tokens):
+        """KV positions a sibling has to reserve beside the prompt blocks it shares with the slot that is prefilled (kv_fits)"""
+        shared = (T // self._kv.block_size) * self._kv.block_size if self._kv is not None else 0
+        return T + max_new_tokens - shared
+
+    def admit_fork(self, st, children, max_new_tokens=1):
+        """Between admit_begin and admit_step of a request with n > 1: the free cache slots `children` become siblings of st's slot.
+        Paged cache: each child gives up its row and reserves private blocks for everything from the trailing, partly filled prompt
+        block on (children write position T next); the whole prompt blocks are shared with the parent's row by reference count once
+        they are written (fork_slots).  When the pool cannot cover a child nothing stays reserved and KvPoolExhausted is raised.
+        The sharing, the copies and the n first tokens follow the prefill (admit_step)."""
+        children = [int(c) for c in children]
+        slot, T = st["slot"], st["T"]
+        if slot in children or len(set(children)) != len(children) or not all(0 <= c < self.max_batch for c in children):
+            raise ValueError(f"fork: children {children} must be distinct cache slots other than {slot}")
+        for c in children:
+            self._slot_idents[c] = []
+            self._kv_replaced.pop(c, None)
+        if self._kv is not None:
+            from .kv_blocks import KvPoolExhausted
+            nshare = T // self._kv.block_size
+            order = sorted(range(self.max_batch), key=lambda sl: len(self._slot_idents[sl]))
+            made = []
+            try:
+                for c in children:
+                    self._kv.release(c)
+                    made.append(c)
+                    self._kv.reserve(c, T + max_new_tokens - nshare * self._kv.block_size, protect={slot, *children}, evict_order=order,
+                                     on_evict=self._kv_evicted)
+            except KvPoolExhausted:
+                for c in made:
+                    self._kv.release(c)
+                self._kv.retire(slot)
+                n0 = st["done"]                      # the admission did not happen: take back what admit_begin counted for it
+                self.prefix_stats["requests"] -= 1
+                self.prefix_stats["hits"] -= int(n0 > 0)
+                self.prefix_stats["tokens_reused"] -= n0
+                self.prefix_stats["tokens_prefilled"] -= T - n0
+                raise
+        st["fork"] = children
+        return st
+
+    def fork_slots(self, src, dst, T):
+        """Device side of the fork: K / V rows [0, T) of cache slot `src` reach the slots `dst` (paged: only the rows of the trailing
+        prompt block - the whole blocks are shared through the tables), and with logit controls on the state row of `src` reaches their
+        rows.  One launch each per CHATTS_FORK_MAX_DST destinations; stream-ordered after the prefill."""
+        B, st = self.buf, _lib.stream_ptr()
+        dst = [int(c) for c in dst]
+        if self._kv is not None:                     # the prompt blocks are written: share the whole ones, table rows to the device
+            for c in dst:
+                self._kv.fork(c, int(src), T // self._kv.block_size)
+                self._push_kv_row(c)
+        kc = _lib.KvCache(k=B["kv_k"].data_ptr(), v=B["kv_v"].data_ptr(), max_ctx=self.max_ctx,
+                          dtype=_lib.KV_F16 if self.kv_cache_dtype == torch.float16 else _lib.KV_F32,
+                          block_table=_lib.ptr(B["kv_table"]), block_size=self.kv_block_size,
+                          table_stride=(self.max_ctx // self.kv_block_size) if self.kv_block_size else 0)
+        if self.kv_block_size:
+            layer_stride, seq_stride, n_blocks = B["kv_k"].stride(0), 0, B["kv_k"].shape[1]
+            t0 = T - T % self.kv_block_size
+        else:
+            layer_stride, seq_stride, n_blocks, t0 = B["kv_k"].stride(1), B["kv_k"].stride(0), 0, 0
+        for i in range(0, len(dst), _lib.FORK_MAX_DST):
+            part = dst[i:i + _lib.FORK_MAX_DST]
+            arr = (C.c_int32 * len(part))(*part)
+            _lib.check(self.lib.chatts_kv_fork(C.byref(kc), self.config.num_hidden_layers, self.plan.nkv, self.max_batch, layer_stride,
+                                               seq_stride, n_blocks, int(src), arr, len(part), t0, T, st))
+            if self._controls_on:
+                V = B["lc_state"].shape[1]
+                _lib.check(self.lib.chatts_logit_state_fork(B["lc_state"].data_ptr(), V, V, self.max_batch, int(src), arr, len(part), st))
+        self.prefix_stats["forks"] = self.prefix_stats.get("forks", 0) + 1
+        self.prefix_stats["fork_children"] = self.prefix_stats.get("fork_children", 0) + len(dst)
+
+    def _first_tokens_forked(self, slot, row, T, children):
+        """logits of x[row], ONCE -> fork -> the first token of `slot` and of every child, each drawn with its own slot's settings (and
+        followed by its own logprobs / counted into its own state where those modes are on).  The decoder is not run again."""
+        _lib.check(self.lib.chatts_decoder_logits(self._decoder, row, _lib.stream_ptr()))
+        self.fork_slots(slot, children, T)           # (before the first selection counts its token into the source's state row)
+        for s in [slot] + list(children):
+            self._select_first(s, T)
 
     def plan_pack(self, candidates, free_slots):
         """Which of the waiting requests should be prefilled TOGETHER (chatts_decoder_prefill_packed).  candidates: list of

@@ -74,7 +74,7 @@ def render_chat(messages, default_system=DEFAULT_SYSTEM):
     return prompt, series
 
 
-def sampling_from_body(body, default_max_tokens=512):
+def sampling_from_body(body, default_max_tokens=512, max_num_seqs=None):
     mt = body.get("max_completion_tokens") or body.get("max_tokens") or default_max_tokens
     temp = body.get("temperature")
     top_p = body.get("top_p")
@@ -90,10 +90,26 @@ def sampling_from_body(body, default_max_tokens=512):
                 if isinstance(v, bool) or not isinstance(v, (int, float)):
                     raise ValueError(f"{name} must be a number, got {v!r}")
                 out[name] = float(v)
+        # n, stop and include_stop_str_in_output: the same rule
+        if body.get("n") is not None:
+            if isinstance(body["n"], bool) or not isinstance(body["n"], int):
+                raise ValueError(f"n must be an integer, got {body['n']!r}")
+            out["n"] = body["n"]
+        if body.get("best_of") is not None:
+            out["best_of"] = body["best_of"]
+        if body.get("stop") is not None and body.get("stop") != []:
+            out["stop"] = body["stop"]
+        if body.get("include_stop_str_in_output") is not None:
+            if not isinstance(body["include_stop_str_in_output"], bool):
+                raise ValueError("include_stop_str_in_output must be a boolean")
+            out["include_stop_str_in_output"] = body["include_stop_str_in_output"]
     except (TypeError, ValueError) as e:
         raise ValueError(f"malformed sampling parameter: {e}")
     from .engine import validate_sampling
     validate_sampling(**out)             # ValueError -> 400 (never reaches the engine thread)
+    if "n" in out:
+        from .engine import validate_n
+        validate_n(out["n"], out.get("best_of"), max_num_seqs)
     return out
 
 
@@ -148,21 +164,7 @@ def completion_logprobs(tokenizer, token_ids, entries, k, offset0=0):
     return d
 
 
-class IncrementalDecoder:
-    """token ids -> text deltas.  Decodes the whole sequence each time and emits the new suffix, holding back a trailing
-    replacement character (an incomplete multi-byte piece), like vLLM's incremental detokenizer."""
-
-    def __init__(self, tokenizer):
-        self.tok, self.ids, self.text = tokenizer, [], ""
-
-    def push(self, new_ids, final=False):
-        self.ids += list(new_ids)
-        full = self.tok.decode(self.ids, skip_special_tokens=True)
-        if not final and full.endswith("�"):
-            full = full[:-1]
-        delta = full[len(self.text):] if full.startswith(self.text) else full
-        self.text = full if full.startswith(self.text) else self.text + delta
-        return delta
+from .detok import IncrementalDecoder  # noqa: E402,F401  (the one host detokeniser; importable from here as before)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -182,13 +184,13 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
         q = asyncio.Queue()
         holder = []
 
-        def on_tokens(r, new, finished):              # called on the engine thread
-            loop.call_soon_threadsafe(q.put_nowait, (list(new), finished, r))
+        def on_tokens(r, new, finished):              # called on the engine thread (n > 1: once per sibling, r.index says which)
+            loop.call_soon_threadsafe(q.put_nowait, (list(new), finished, r, int(getattr(r, "index", 0) or 0), getattr(r, "text", None)))
         engine_thread.submit(prompt=prompt, timeseries=series, on_tokens=on_tokens, holder=holder, **sp)
         return holder, q
 
     async def next_event(q):
-        """next (new_tokens, finished, request) of a request; a dead engine thread surfaces as an error instead of a hang"""
+        """next (new_tokens, finished, request, choice index, engine text) of a request; a dead engine thread surfaces as an error instead of a hang"""
         while True:
             try:
                 return await asyncio.wait_for(q.get(), timeout=5.0)
@@ -221,7 +223,7 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
                     raise ValueError(f"prompt holds {prompt.count('<ts><ts/>')} <ts><ts/> placeholders but {len(series)} timeseries")
             if len(series) > limit_timeseries:
                 raise ValueError(f"At most {limit_timeseries} timeseries may be provided in one prompt, got {len(series)}")
-            sp = sampling_from_body(body, default_max_tokens)
+            sp = sampling_from_body(body, default_max_tokens, getattr(getattr(engine_thread, "engine", None), "nslots", None))
             lpk = logprobs_from_body(body, chat, max_logprobs)
             if lpk is not None:                  # (only then: an engine without logprobs never sees the keyword)
                 sp["logprobs"] = lpk
@@ -234,76 +236,107 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
             holder, q = await run(prompt, series, sp, loop)
         except RuntimeError as e:
             return error(500, str(e), "server_error")
-        dec = IncrementalDecoder(tokenizer)
-        lp_state = {"n": 0, "offset": 0}               # tokens whose entries were delivered; completions' text_offset so far
+        n = int(sp.get("n", 1))
+        use_engine_text = bool(sp.get("stop"))         # stop strings: the engine's own decode decides what may be shown
+        # per choice: its decoder, the text sent so far, delivered logprob entries / completions' text_offset, the last request object
+        state = [{"dec": IncrementalDecoder(tokenizer), "sent": "", "n": 0, "offset": 0, "r": None, "first": True} for _ in range(n)]
 
-        def lp_part(new, r):
+        def lp_part(new, r, st):
             """the choice's `logprobs` for the tokens `new` just delivered (None when the request did not ask)"""
             if lpk is None:
                 return None
-            n = lp_state["n"]
-            entries = list(r.logprobs[n:n + len(new)])
-            lp_state["n"] = n + len(new)
+            k = st["n"]
+            entries = list(r.logprobs[k:k + len(new)])
+            st["n"] = k + len(new)
             if chat:
                 return {"content": chat_logprobs_content(tokenizer, new, entries, lpk)}
-            d = completion_logprobs(tokenizer, new, entries, lpk, lp_state["offset"])
-            lp_state["offset"] += sum(len(t) for t in d["tokens"])
+            d = completion_logprobs(tokenizer, new, entries, lpk, st["offset"])
+            st["offset"] += sum(len(t) for t in d["tokens"])
             return d
 
-        def chunk(delta_text, finish=None, first=False, logprobs=None):
+        def delta_text(st, new, finished, text):
+            """the text this event adds to the choice (stop strings: from the engine's text, which holds back what may still turn
+            out to be the beginning of a stop string; otherwise from the choice's own incremental decoder)"""
+            if not use_engine_text or text is None:
+                d = st["dec"].push(new, final=finished)
+                st["sent"] = st["dec"].text
+                return d
+            d = text[len(st["sent"]):] if text.startswith(st["sent"]) else ""
+            st["sent"] += d
+            return d
+
+        def chunk(index, delta_text, finish=None, first=False, logprobs=None):
             if chat:
                 delta = {"content": delta_text} if delta_text or not first else {}
                 if first:
                     delta = {"role": "assistant", "content": delta_text}
-                ch = {"index": 0, "delta": delta, "finish_reason": finish}
+                ch = {"index": index, "delta": delta, "finish_reason": finish}
             else:
-                ch = {"index": 0, "text": delta_text, "finish_reason": finish}
+                ch = {"index": index, "text": delta_text, "finish_reason": finish}
             if logprobs is not None:
                 ch["logprobs"] = logprobs
             return {"id": rid, "object": obj + ".chunk" if chat else obj, "created": int(time.time()), "model": model_name, "choices": [ch]}
 
         if body.get("stream"):
             async def gen():
-                first = True
-                while True:
+                left = n
+                while left:
                     try:
-                        new, finished, r = await next_event(q)
+                        new, finished, r, idx, text = await next_event(q)
                     except RuntimeError as e:
                         yield "data: " + json.dumps({"error": {"message": str(e), "type": "server_error"}}) + "\n\n"
                         break
                     if r.error is not None:
                         yield "data: " + json.dumps({"error": {"message": str(r.error), "type": "invalid_request_error"}}) + "\n\n"
                         break
-                    text = dec.push(new, final=finished)
-                    part = lp_part(new, r) if new else None
-                    if text or first or part is not None:
-                        yield "data: " + json.dumps(chunk(text, None, first, part)) + "\n\n"
-                        first = False
+                    st = state[idx]
+                    d = delta_text(st, new, finished, text)
+                    part = lp_part(new, r, st) if new else None
+                    if d or st["first"] or part is not None:
+                        yield "data: " + json.dumps(chunk(idx, d, None, st["first"], part)) + "\n\n"
+                        st["first"] = False
                     if finished:
-                        yield "data: " + json.dumps(chunk("", r.finish_reason)) + "\n\n"
-                        break
+                        yield "data: " + json.dumps(chunk(idx, "", r.finish_reason)) + "\n\n"
+                        left -= 1
                 yield "data: [DONE]\n\n"
             return StreamingResponse(gen(), media_type="text/event-stream")
-        while True:
+        left = n
+        while left:
             try:
-                new, finished, r = await next_event(q)
+                new, finished, r, idx, text = await next_event(q)
             except RuntimeError as e:
                 return error(500, str(e), "server_error")
             if r.error is not None:
                 return error(400, str(r.error))
-            dec.push(new, final=finished)
+            st = state[idx]
+            delta_text(st, new, finished, text)
             if finished:
-                break
-        lp_all = lp_part(list(r.tokens), r)
-        usage = {"prompt_tokens": r.prompt_tokens, "completion_tokens": len(r.tokens), "total_tokens": r.prompt_tokens + len(r.tokens)}
-        if chat:
-            choice = {"index": 0, "message": {"role": "assistant", "content": dec.text}, "finish_reason": r.finish_reason}
-        else:
-            choice = {"index": 0, "text": dec.text, "finish_reason": r.finish_reason}
-        if lp_all is not None:
-            choice["logprobs"] = lp_all
-        return {"id": rid, "object": obj, "created": int(time.time()), "model": model_name, "choices": [choice], "usage": usage,
-                "token_ids": list(r.tokens)}
+                st["r"] = r
+                if use_engine_text and text is not None:
+                    st["sent"] = text              # the finished request's own text (what LLM.generate returns), not a sum of deltas
+                left -= 1
+        choices, completion_tokens = [], 0
+        for idx, st in enumerate(state):
+            r = st["r"]
+            lp_all = lp_part(list(r.tokens), r, st)
+            completion_tokens += len(r.tokens)
+            if chat:
+                choice = {"index": idx, "message": {"role": "assistant", "content": st["sent"]}, "finish_reason": r.finish_reason}
+            else:
+                choice = {"index": idx, "text": st["sent"], "finish_reason": r.finish_reason}
+            if getattr(r, "stop_reason", None) is not None:
+                choice["stop_reason"] = r.stop_reason
+            if lp_all is not None:
+                choice["logprobs"] = lp_all
+            if n > 1:
+                choice["token_ids"] = list(r.tokens)
+            choices.append(choice)
+        r0 = state[0]["r"]
+        usage = {"prompt_tokens": r0.prompt_tokens, "completion_tokens": completion_tokens, "total_tokens": r0.prompt_tokens + completion_tokens}
+        out = {"id": rid, "object": obj, "created": int(time.time()), "model": model_name, "choices": choices, "usage": usage}
+        if n == 1:
+            out["token_ids"] = list(r0.tokens)
+        return out
 
     @app.post("/v1/chat/completions")
     async def chat_completions(request: Request):

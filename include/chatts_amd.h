@@ -538,6 +538,29 @@ int chatts_logit_state_reset(int32_t* state_row, int64_t vocab, int64_t vocab_of
 int chatts_logit_state_update(int32_t* state, int64_t state_stride, int batch, int64_t vocab, int64_t vocab_offset,
                               const int64_t* token, chatts_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fork (kv_fork.hip): n samples of one prompt from ONE prefill.  What the siblings need from the prompt - its K / V rows and, with
+ * logit controls, the prompt marks of the state row - is copied from the slot that was prefilled to m other slots in one launch each:
+ * every 16-byte unit of the source is read once and written m times, a wave access covers whole rows.  The first tokens are then m + 1
+ * selections from the one logits row of the prefill (chatts_decoder_select_tokens / chatts_sample_batched with each sibling's settings).
+ * Both entry points validate on the host, enqueue one kernel, neither allocate nor synchronise, and are graph-capturable; the
+ * destination list is a HOST array (1 .. CHATTS_FORK_MAX_DST entries, distinct, none equal to the source) that travels in the kernel
+ * arguments.
+ *   chatts_kv_fork           rows [t0, t1) of every (layer, kv head) of K and of V: slot src_slot -> slots dst_slots[0 .. m).
+ *                            cache->k / cache->v: layer 0 of slot 0 (contiguous form; slot s / layer l at s * seq_stride + l * layer_stride
+ *                            elements) or layer 0's block pool (paged form: layer l at l * layer_stride, seq_stride ignored; n_blocks = blocks
+ *                            in a layer's pool; the rows are found through the table rows of the source and of each destination, and a table
+ *                            entry outside 0 .. n_blocks - 1 is skipped, never followed).  Strides count elements of cache->dtype.  Paged
+ *                            callers share the whole prompt blocks between the table rows themselves and pass only the trailing, partly
+ *                            filled block: t0 = t1 - t1 % block_size.  t0 == t1 enqueues nothing.
+ *   chatts_logit_state_fork  row src_row of the int32 state [n_rows, state_stride] (cells 0 .. vocab - 1) -> rows dst_rows[0 .. m)
+ * ------------------------------------------------------------------------------------------- */
+#define CHATTS_FORK_MAX_DST 64
+int chatts_kv_fork(const ChattsKvCache* cache, int n_layers, int n_kv, int n_slots, int64_t layer_stride, int64_t seq_stride,
+                   int n_blocks, int src_slot, const int32_t* dst_slots, int m, int t0, int t1, chatts_stream_t stream);
+int chatts_logit_state_fork(int32_t* state, int64_t state_stride, int64_t vocab, int n_rows, int src_row, const int32_t* dst_rows, int m,
+                            chatts_stream_t stream);
+
 /* x[h] = float(table[*token - vocab_offset, h]) : next-step input embedding, token id read on the device. */
 int chatts_embed_token(const int64_t* token_dev, const chatts_bf16* table, int64_t vocab_offset,
                        int64_t vocab_rows, int hidden, float* out, chatts_stream_t stream);
