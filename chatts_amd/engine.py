@@ -18,71 +18,8 @@ from collections import deque
 
 import numpy as np
 
-
-def validate_controls(repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None):
-    """The four logit controls with vLLM's defaults and ranges -> (r, f, p, min_p) as floats (None = the default); ValueError otherwise."""
-    import math
-    vals = []
-    for name, v, default in (("repetition_penalty", repetition_penalty, 1.0), ("frequency_penalty", frequency_penalty, 0.0),
-                             ("presence_penalty", presence_penalty, 0.0), ("min_p", min_p, 0.0)):
-        v = default if v is None else v
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-        vals.append(float(v))
-    r, f, p, m = vals
-    if not r > 0.0:
-        raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
-    if not -2.0 <= f <= 2.0:
-        raise ValueError(f"frequency_penalty must be in [-2, 2], got {frequency_penalty}")
-    if not -2.0 <= p <= 2.0:
-        raise ValueError(f"presence_penalty must be in [-2, 2], got {presence_penalty}")
-    if not 0.0 <= m <= 1.0:
-        raise ValueError(f"min_p must be in [0, 1], got {min_p}")
-    return r, f, p, m
-
-
-NO_CONTROLS = (1.0, 0.0, 0.0, 0.0)
-
-
-def validate_n(n=None, best_of=None, max_num_seqs=None):
-    """n (samples per prompt, vLLM's name) -> int >= 1; best_of only as None or equal to n (vLLM V1 removed it); siblings are admitted
-    together, so n may not exceed max_num_seqs (checked when given).  ValueError otherwise."""
-    n = 1 if n is None else n
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
-        raise ValueError(f"n must be an integer >= 1, got {n!r}")
-    if best_of is not None and (isinstance(best_of, bool) or not isinstance(best_of, (int, np.integer)) or int(best_of) != int(n)):
-        raise ValueError(f"best_of is accepted only as None or equal to n={n}, got {best_of!r}")
-    if max_num_seqs is not None and int(n) > int(max_num_seqs):
-        raise ValueError(f"n={n} exceeds max_num_seqs={max_num_seqs}: the samples of one prompt are admitted together")
-    return int(n)
-
-
-def validate_sampling(max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, logprobs=None, max_logprobs=20, prompt_logprobs=None,
-                      repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None, n=None, best_of=None,
-                      stop=None, **_):
-    """The ranges vLLM's SamplingParams accepts (what the reference's drivers pass: inference_tsmllm_vllm.py:43-46,
-    llm_utils.py:153).  Raises ValueError - the server turns it into a 400 - BEFORE the request can reach the engine thread, where
-    an out-of-range value would otherwise surface inside set_sampling / chatts_decoder_set_sampling."""
-    import math
-    from .detok import normalize_stop
-    validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
-    validate_n(n, best_of)
-    normalize_stop(stop)
-    t = 0.0 if temperature is None else float(temperature)
-    if not math.isfinite(t) or t < 0.0:
-        raise ValueError(f"temperature must be a finite number >= 0, got {temperature}")
-    p = 1.0 if top_p is None else float(top_p)
-    if not math.isfinite(p) or not (0.0 < p <= 1.0):
-        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
-    if int(top_k or 0) < -1:
-        raise ValueError(f"top_k must be -1 / 0 (off) or positive, got {top_k}")
-    if int(max_tokens) < 1:
-        raise ValueError(f"max_tokens must be at least 1, got {max_tokens}")
-    if prompt_logprobs is not None:
-        raise ValueError("prompt_logprobs is not supported (only the logprobs of generated tokens)")
-    if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer))
-                                 or not 0 <= int(logprobs) <= int(max_logprobs)):
-        raise ValueError(f"logprobs must be an integer in 0..{max_logprobs} (max_logprobs), got {logprobs!r}")
+from .sampling import (NO_CONTROLS, REQUEST_FIELDS, request_settings, validate_controls, validate_n,  # noqa: F401  (re-exported)
+                       validate_sampling)
 
 
 class ExchangeBroken(RuntimeError):
@@ -91,25 +28,47 @@ class ExchangeBroken(RuntimeError):
     on - EngineThread fails every request, releases the followers, and a supervisor restarts all ranks."""
 
 
+_DEFAULT_SETTINGS = {**request_settings(max_tokens=1), "seed": 0}
+
+
 class Request:
-    def __init__(self, rid, prompt, timeseries, max_tokens, sampling_key, eos, on_tokens):
-        self.rid, self.prompt, self.timeseries, self.max_tokens = rid, prompt, timeseries, int(max_tokens)
-        self.sampling_key, self.eos, self.on_tokens = sampling_key, set(eos or ()), on_tokens
+    """One request and its settings (sampling.request_settings: Engine.check made them).  `mixed`: the model keeps per-slot sampling
+    settings, so requests do not form sampling groups - `sampling_key` then only says whether this one samples."""
+
+    def __init__(self, rid, prompt, timeseries, on_tokens=None, model_eos=(), mixed=False, **settings):
+        s = self.settings = {**_DEFAULT_SETTINGS, **settings}
+        self.rid, self.prompt, self.timeseries, self.on_tokens, self.max_tokens = rid, prompt, timeseries, on_tokens, s["max_tokens"]
+        self._model_eos, self._mixed = model_eos, mixed
+        self.eos = set(() if s["ignore_eos"] else model_eos) | set(s["stop_token_ids"])
+        self.stop_ids = {int(t) for t in s["stop_token_ids"]}
+        key = (s["temperature"], s["top_k"], s["top_p"], s["seed"]) if s["temperature"] else None
+        self.sampling = (0.0, 0, 1.0, 0) if key is None else key       # (temperature, top_k, top_p, seed): the slot's settings
+        self.sampling_key = key if not mixed else "rows" if key else None
+        self.controls = s["controls"]        # (repetition_penalty, frequency_penalty, presence_penalty, min_p)
         self.tokens, self.sent, self.finished, self.finish_reason = [], 0, False, None
         self.prompt_tokens = 0
         # logprobs=k: one (logprob, rank, [(id, logprob)] * k) entry per token of `tokens`, grown with it; None when not asked
-        self.logprob_k, self.logprobs, self.cumulative_logprob = None, None, None
+        self.logprob_k = s["logprobs"]
+        self.logprobs, self.cumulative_logprob = (None, None) if self.logprob_k is None else ([], 0.0)
         self.t_arrival, self.t_first = time.perf_counter(), None
         self.error = None
-        self.controls = NO_CONTROLS          # (repetition_penalty, frequency_penalty, presence_penalty, min_p): Engine.add_request
         self.bypassed = 0                    # later arrivals admitted past this request while it waited for its sampling group
+        # stop strings: `text` is then the engine's own decode (what a stream may show so far; the final text once finished)
+        self.stop, self.include_stop, self.checker, self.text = s["stop"], s["include_stop"], None, None
+        self.stop_reason = None              # the matched stop string, the id of a stop_token_ids hit, None for EOS / length
         # n > 1 (parallel sampling): the request the caller holds is the PARENT - it never occupies a slot; `children` are the n
         # sequences (index 0 .. n-1, each with the fields of a request of its own), `remaining` those still running
-        self.n, self.index, self.parent, self.children, self.remaining = 1, 0, None, None, 0
-        # stop strings: `text` is then the engine's own decode (what a stream may show so far; the final text once finished)
-        self.stop, self.include_stop, self.checker, self.text = [], False, None, None
-        self.stop_reason = None              # the matched stop string, the id of a stop_token_ids hit, None for EOS / length
-        self.stop_ids = set()
+        self.n, self.index, self.parent, self.children, self.remaining = s["n"], 0, None, None, 0
+        if self.n > 1:
+            self.remaining, self.children = self.n, [self.child(i) for i in range(self.n)]
+
+    def child(self, i):
+        """sibling i of a request with n > 1: every setting of the parent, its own seed (+ i mod 2^32), the parent's arrival time"""
+        c = Request(self.rid, self.prompt, self.timeseries, self.on_tokens, self._model_eos, self._mixed,
+                    **{**self.settings, "n": 1, "seed": (self.settings["seed"] + i) & 0xFFFFFFFF})
+        c.sampling = self.sampling[:3] + (c.settings["seed"],)         # (a greedy row keeps its seed too)
+        c.index, c.parent, c.t_arrival = i, self, self.t_arrival
+        return c
 
     @property
     def outputs(self):
@@ -122,13 +81,11 @@ class Engine:
 
     def __init__(self, model, processor, sync_every=4, prefill_chunk_tokens=None, greedy_return_steps=256):
         self.model, self.processor = model, processor
-        # per-slot sampling: scheduler iterations without any sampling request (running or waiting) after which the step goes back from the
-        # per-row sampler to the plain argmax tail (a graph re-capture); 0 = stay in per-row mode once entered.  Every rank of a
-        # tensor-parallel group counts the same iterations (followers replay the leader's), so all of them switch together.
+        # the modes of the decode step (per-row sampling, logprobs, logit controls): scheduler iterations without any request that needs
+        # one (running or waiting) after which it is switched off again (a graph re-capture); 0 = stay in a mode once entered.  Every rank
+        # of a tensor-parallel group counts the same iterations (followers replay the leader's), so all of them switch together.
         self.greedy_return_steps = max(0, int(greedy_return_steps))
-        self._greedy_iters = 0
-        self._no_logprob_iters = 0
-        self._no_control_iters = 0
+        self._idle = {}                                 # mode -> consecutive iterations nobody needed it (_mode)
         self.sync_every = max(1, int(sync_every))       # decode steps between device->host token reads
         # chunked-prefill scheduling (vLLM: enable_chunked_prefill / max_num_batched_tokens): while other sequences are decoding, a
         # long prompt is prefilled this many rows per scheduler iteration, each followed by one decode step of the running batch,
@@ -148,106 +105,45 @@ class Engine:
             model.buf["pos_all"].fill_(-1)            # every slot starts parked
 
     # ---- requests ---------------------------------------------------------------------------------
-    def add_request(self, prompt, timeseries=None, max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, seed=None,
-                    stop_token_ids=None, ignore_eos=False, on_tokens=None, logprobs=None, repetition_penalty=None,
-                    frequency_penalty=None, presence_penalty=None, min_p=None, n=1, best_of=None, stop=None,
-                    include_stop_str_in_output=False):
-        """seed None: per-slot mode gives every request its own stream (a hash of its arrival number - vLLM's seed=None means "not
+    def check(self, **settings):
+        """The one check of a request's settings (sampling.REQUEST_FIELDS): their value ranges, and what THIS engine cannot serve - n >
+        max_num_seqs, n > 1 on a model without per-slot sampling settings or without a fork, stop strings without a tokenizer, logit
+        controls or logprobs on a model without them.  ValueError, or -> the normalised settings (sampling.request_settings).
+        add_request calls it; EngineThread calls it BEFORE a request is announced to the follower ranks."""
+        s = request_settings(**settings, max_logprobs=self.max_logprobs, max_num_seqs=self.nslots)
+        if s["n"] > 1 and not self.mixed:
+            raise ValueError("n > 1 needs a model with per-slot sampling settings (set_slot_sampling)")
+        if s["n"] > 1 and not hasattr(self.model, "admit_fork"):
+            raise ValueError("this model cannot fork a prompt into several samples (n > 1)")
+        if s["stop"] and getattr(self.processor, "tokenizer", None) is None:
+            raise ValueError("stop strings need a tokenizer (the engine's processor has none)")
+        if s["controls"] != NO_CONTROLS and not hasattr(self.model, "set_slot_controls"):
+            raise ValueError("this model does not apply repetition / frequency / presence penalties or min_p")
+        if s["logprobs"] is not None and not hasattr(self.model, "set_logprobs"):
+            raise ValueError("this model does not compute logprobs")
+        return s
+
+    def add_request(self, prompt, timeseries=None, on_tokens=None, **settings):
+        """settings: sampling.REQUEST_FIELDS (max_tokens=64, temperature=0.0, top_p=1.0, top_k=0, seed=None, stop_token_ids, ignore_eos,
+        logprobs, the four logit controls, n=1, best_of, stop, include_stop_str_in_output), checked by check().
+        seed None: per-slot mode gives every request its own stream (a hash of its arrival number - vLLM's seed=None means "not
         reproducible across requests"; here two identical prompts still differ, and a rerun of the same arrival order repeats);
         grouped mode uses 0 (requests that decode together must share ONE configuration there).
         n > 1: -> the parent request; its `children` are n sequences of the one prompt, child i drawing with seed + i (mod 2^32), all
         admitted together from ONE prefill (step()).  on_tokens is called per child (`r.index`, `r.parent`).
         stop: strings that end a sequence when they appear in its decoded text (chatts_amd/detok.py: the rule)."""
-        validate_sampling(max_tokens, temperature, top_p, top_k, logprobs=logprobs, max_logprobs=self.max_logprobs)
-        n, stop = self.check_request(n, best_of, stop)
-        controls = validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
-        if controls != NO_CONTROLS and not hasattr(self.model, "set_slot_controls"):
-            raise ValueError("this model does not apply repetition / frequency / presence penalties or min_p")
-        if logprobs is not None and not hasattr(self.model, "set_logprobs"):
-            raise ValueError("this model does not compute logprobs")
-        if seed is None:
-            seed = ((self._rid + 1) * 2654435761) & 0xFFFFFFFF if self.mixed else 0
+        s = self.check(**settings)
+        if s["seed"] is None:
+            s["seed"] = ((self._rid + 1) * 2654435761) & 0xFFFFFFFF if self.mixed else 0
         e = self.model.config.eos_token_id
-        eos = [] if ignore_eos else (list(e) if isinstance(e, (list, tuple)) else [e])
-        eos += list(stop_token_ids or [])
-        key = None if not temperature else (float(temperature), max(int(top_k or 0), 0), float(top_p), int(seed))
         self._rid += 1
-        r = Request(self._rid, prompt, list(timeseries or []), max_tokens, key, eos, on_tokens)
-        r.sampling = (0.0, 0, 1.0, 0) if key is None else key
-        r.controls = controls                # (repetition_penalty, frequency_penalty, presence_penalty, min_p)
-        if logprobs is not None:
-            r.logprob_k, r.logprobs, r.cumulative_logprob = int(logprobs), [], 0.0
-        if self.mixed:
-            r.sampling_key = "rows" if key is not None else None     # one group: who samples is a per-slot matter
-        r.stop, r.include_stop, r.stop_ids = stop, bool(include_stop_str_in_output), {int(t) for t in (stop_token_ids or [])}
-        if n > 1:
-            r.n, r.remaining, r.children = n, n, []
-            for i in range(n):
-                c = Request(r.rid, prompt, r.timeseries, max_tokens, r.sampling_key, eos, on_tokens)
-                c.index, c.parent, c.controls, c.t_arrival = i, r, controls, r.t_arrival
-                c.sampling = r.sampling[:3] + ((int(seed) + i) & 0xFFFFFFFF,)
-                c.stop, c.include_stop, c.stop_ids = stop, r.include_stop, r.stop_ids
-                if logprobs is not None:
-                    c.logprob_k, c.logprobs, c.cumulative_logprob = int(logprobs), [], 0.0
-                r.children.append(c)
+        r = Request(self._rid, prompt, list(timeseries or []), on_tokens, list(e) if isinstance(e, (list, tuple)) else [e], self.mixed, **s)
         self.waiting.append(r)
         return r
-
-    def check_request(self, n=None, best_of=None, stop=None, **_):
-        """What this engine refuses about n and stop beyond their value ranges (ValueError): n > max_num_seqs, n > 1 on a model without
-        per-slot sampling settings or without a fork, stop strings without a tokenizer.  -> (n, list of stop strings).  add_request
-        calls it; EngineThread calls it BEFORE a request is announced to the follower ranks."""
-        from .detok import normalize_stop
-        n = validate_n(n, best_of, self.nslots)
-        stop = normalize_stop(stop)
-        if n > 1 and not self.mixed:
-            raise ValueError("n > 1 needs a model with per-slot sampling settings (set_slot_sampling)")
-        if n > 1 and not hasattr(self.model, "admit_fork"):
-            raise ValueError("this model cannot fork a prompt into several samples (n > 1)")
-        if stop and getattr(self.processor, "tokenizer", None) is None:
-            raise ValueError("stop strings need a tokenizer (the engine's processor has none)")
-        return n, stop
 
     @property
     def max_logprobs(self):
         return int(getattr(self.model, "max_logprobs", 20))
-
-    def _logprobs_mode(self):
-        """Logprobs on while any running, prefilling or waiting request asks for them; off again after `greedy_return_steps`
-        consecutive iterations without one (the sampling mode's hysteresis, for the same reason: a switch re-captures the graphs;
-        0 = stay on once on).  Followers replay the leader's requests and count the same iterations: all ranks switch together."""
-        if not hasattr(self.model, "set_logprobs"):
-            return
-        want = (any(r is not None and r.logprob_k is not None for r in self.slots) or
-                (self.prefilling is not None and self.prefilling[0].logprob_k is not None) or
-                any(q.logprob_k is not None for q in self.waiting))
-        on = bool(getattr(self.model, "_logprobs_on", False))
-        if want:
-            self._no_logprob_iters = 0
-            if not on:
-                self.model.set_logprobs(True)
-        elif on:
-            self._no_logprob_iters += 1
-            if self.greedy_return_steps and self._no_logprob_iters >= self.greedy_return_steps:
-                self.model.set_logprobs(False)
-
-    def _controls_mode(self):
-        """The model's logit-controls mode on while any running, prefilling or waiting request has a penalty or min_p; off again after
-        `greedy_return_steps` consecutive iterations without one (the hysteresis of _logprobs_mode, for the same reason)."""
-        if not hasattr(self.model, "set_logit_controls"):
-            return
-        want = (any(r is not None and r.controls != NO_CONTROLS for r in self.slots) or
-                (self.prefilling is not None and self.prefilling[0].controls != NO_CONTROLS) or
-                any(q.controls != NO_CONTROLS for q in self.waiting))
-        on = bool(getattr(self.model, "_controls_on", False))
-        if want:
-            self._no_control_iters = 0
-            if not on:
-                self.model.set_logit_controls(True)
-        elif on:
-            self._no_control_iters += 1
-            if self.greedy_return_steps and self._no_control_iters >= self.greedy_return_steps:
-                self.model.set_logit_controls(False)
 
     def has_work(self):
         return bool(self.waiting) or self.prefilling is not None or any(s is not None for s in self.slots)
@@ -268,25 +164,31 @@ class Engine:
             self.model.set_sampling(key[0], key[1], key[2], key[3])
         self.active_key = key
 
-    def _mixed_mode(self):
-        """Per-slot mode: the step draws per row (greedy rows included) while any running or waiting request samples, and goes back
-        to the plain argmax tail when nobody does.  Every slot's settings are current at all times, so the switch is safe whenever."""
-        want = "rows" if (any(r is not None and r.sampling_key for r in self.slots) or
-                          (self.prefilling is not None and self.prefilling[0].sampling_key) or
-                          any(q.sampling_key for q in self.waiting)) else None
-        if want is None and self.active_key == "rows":
-            # Hysteresis instead of either extreme.  Every switch drops both captured hipGraphs (re-capture + a warm eager step on all
-            # ranks), so alternating traffic must not flip the mode per request; but staying in per-row mode for good would leave later
-            # greedy traffic on the sampler path (under TP: a full-vocabulary all-gather + the sampler kernel per step instead of the
-            # 2-word tp_argmax).  So: back to the argmax tail after `greedy_return_steps` consecutive iterations without any sampling
-            # request running or waiting (0 = never switch back).
-            self._greedy_iters = getattr(self, "_greedy_iters", 0) + 1
-            if not self.greedy_return_steps or self._greedy_iters < self.greedy_return_steps:
-                return
-        if want == "rows":
-            self._greedy_iters = 0
-        if want != self.active_key:
-            self._apply_sampling(want)
+    def _requests_in_flight(self):
+        """every request that will still draw a token: running, being prefilled, waiting"""
+        yield from (r for r in self.slots if r is not None)
+        if self.prefilling is not None:
+            yield self.prefilling[0]
+        yield from self.waiting
+
+    def _mode(self, name, wanted, on, switch):
+        """One mode of the decode step (per-row sampling, logprobs, logit controls): on while any request in flight wants it
+        (`wanted(request)`), off again when nobody has for a while.  `on`: the model's current state; `switch(bool)` changes it.
+        The per-row sampler draws greedy rows too and every slot's settings are current at all times, so a switch is safe whenever.
+        Hysteresis instead of either extreme.  Every switch drops both captured hipGraphs (re-capture + a warm eager step on all
+        ranks), so alternating traffic must not flip the mode per request; but staying in per-row mode for good would leave later
+        greedy traffic on the sampler path (under TP: a full-vocabulary all-gather + the sampler kernel per step instead of the
+        2-word tp_argmax).  So: back to the plain step after `greedy_return_steps` consecutive iterations without any request that
+        wants the mode running or waiting (0 = never switch back).  Followers replay the leader's requests and count the same
+        iterations: all ranks switch together."""
+        if any(wanted(r) for r in self._requests_in_flight()):
+            self._idle[name] = 0
+            if not on:
+                switch(True)
+        elif on:
+            self._idle[name] = self._idle.get(name, 0) + 1
+            if self.greedy_return_steps and self._idle[name] >= self.greedy_return_steps:
+                switch(False)
 
     def _emit(self, r, finished, reason=None):
         new = r.tokens[r.sent:]
@@ -297,11 +199,76 @@ class Engine:
             r.on_tokens(r, new, finished)
 
     def _fail(self, r, e, done):
+        """the one way a request ends with an error (a bad request must not take the engine down); n > 1: its samples with it"""
         r.error = e
         for c in (r.children or ()):
             c.error, c.finished, c.finish_reason = e, True, "error"
         self._emit(r, True, "error")
         done.append(r)
+
+    def _running(self):
+        return any(v is not None for v in self.slots)
+
+    # ---- admission --------------------------------------------------------------------------------
+    def _candidates(self, free):
+        """The waiting requests that may be admitted into the `free` slots now, in arrival order ([]: nobody).  A request with n > 1
+        at the head goes alone, once n slots are free.  Requests that share the running batch's sampling configuration may overtake
+        a head of the queue that waits for ANOTHER one (it joins when the batch has drained), and single requests a head that waits
+        for n slots - but only `max_bypass` times, or a steady stream of such arrivals would starve it."""
+        head = self.waiting[0]
+        if head.n > 1:
+            if head.n <= len(free):
+                return [head]
+            blocked = True
+        else:
+            blocked = not self.mixed and head.sampling_key != self.active_key
+        if blocked and head.bypassed >= self.max_bypass:
+            return []
+        if self.mixed:
+            cands = []
+            for q in self.waiting:                       # a later request with n > 1 ends the run (it goes first then)
+                if q.n > 1:
+                    if q is head:
+                        continue
+                    break
+                cands.append(q)
+        else:
+            cands = [q for q in self.waiting if q.sampling_key == self.active_key]
+        cands = cands[:len(free)]
+        if blocked:
+            head.bypassed += len(cands)
+        return cands
+
+    def _encoded(self, r, done):
+        """tokenise / sp-encode once per request -> True; a request that cannot be encoded is failed (and no longer waits)"""
+        if getattr(r, "_enc", None) is None:
+            try:
+                r._enc = self._encode(r)
+                r.prompt_tokens = len(r._enc[0])
+            except Exception as e:
+                self.waiting.remove(r)
+                self._fail(r, e, done)
+                return False
+        return True
+
+    def _needs(self, r):
+        """KV positions of r's sequences (n > 1: the shared whole prompt blocks are counted once, with sample 0)"""
+        m = self.model
+        T = m.request_tokens(*r._enc)
+        return [T + r.max_tokens] + ([m.fork_tokens(T, r.max_tokens)] * (r.n - 1) if r.n > 1 else [])
+
+    def _pool_gate(self, needs):
+        """block-paged cache with an oversubscribed pool -> "admit"; "wait" until a running sequence finishes (its blocks become
+        evictable); "never" when nothing is running: the request can never fit"""
+        if self.model.kv_fits(needs):
+            return "admit"
+        return "wait" if self._running() else "never"
+
+    def _write_settings(self, slot, r):
+        """the slot's sampling settings and logit controls, before its first token is drawn (per-slot mode)"""
+        self.model.set_slot_sampling(slot, *r.sampling)
+        if hasattr(self.model, "set_slot_controls"):
+            self.model.set_slot_controls(slot, *r.controls)
 
     def _place(self, r, s, st=None):
         """the admission of r into slot s is complete: it runs from now on (n > 1: its children, in s and the forked slots)"""
@@ -312,55 +279,83 @@ class Engine:
         else:
             self.slots[s], self.produced[s] = r, 1
 
-    def _admit_parent(self, r, free, done):
-        """Admission of a request with n > 1 (the head of the queue; n slots are free): ONE preparation and ONE prefill into the slot
-        child 0 takes, the other n - 1 slots are forked from it (model.admit_fork / admit_step).  -> "ok", "failed" (the request was
-        answered with an error) or "wait" (the block pool cannot hold it yet, or its prompt is now being prefilled in chunks)."""
-        m = self.model
-        if getattr(r, "_enc", None) is None:
-            try:
-                r._enc = self._encode(r)
-                r.prompt_tokens = len(r._enc[0])
-            except Exception as e:
-                self.waiting.remove(r)
-                self._fail(r, e, done)
-                return "failed"
-        ids, ser, lens = r._enc
-        if getattr(m, "_kv_dynamic", False):
-            T = m.request_tokens(ids, ser, lens)
-            need = [T + r.max_tokens] + [m.fork_tokens(T, r.max_tokens)] * (r.n - 1)      # shared prompt blocks counted once
-            if not m.kv_fits(need):
-                if any(v is not None for v in self.slots):
-                    return "wait"
-                self.waiting.remove(r)
-                self._fail(r, RuntimeError(f"request needs {sum(need)} KV positions for its {r.n} samples, more than the block pool "
-                                           f"can hold ({m.kv_stats()})"), done)
-                return "failed"
-        s = m.pick_slot(list(free), m._request_idents(ids, ser, lens)) if hasattr(m, "pick_slot") else free[0]
-        kids = [f for f in free if f != s][:r.n - 1]
-        self.waiting.remove(r)
-        for c, sl in zip(r.children, [s] + kids):        # every sibling's own settings, before its first token is drawn
-            m.set_slot_sampling(sl, *c.sampling)
-            if hasattr(m, "set_slot_controls"):
-                m.set_slot_controls(sl, *c.controls)
-        try:
-            st = m.admit_fork(m.admit_begin(s, ids, ser, lens, r.max_tokens), kids, r.max_tokens)
-            if (self.prefill_chunk_tokens and any(v is not None for v in self.slots)
-                    and st["T"] - st["done"] > self.prefill_chunk_tokens):
-                self.prefilling = (r, s, st)             # others are decoding: the one prefill goes in chunks between their steps
-                m.admit_step(st, self.prefill_chunk_tokens)
-                return "wait"
+    def _start(self, group, items, kids):
+        """Prefill what was picked: several short prompts in one packed pass, otherwise one request (n > 1: ONE prefill into the slot
+        sample 0 takes, the slots `kids` are forked from it) - in chunks between the others' decode steps when it is long and others
+        are decoding.  -> False when the prompt is now `self.prefilling`: no other admission until it is in."""
+        m, r, chunk, st = self.model, group[0], self.prefill_chunk_tokens, None
+        if len(items) > 1:
+            m._admit_packed(items)
+        elif self.nslots == 1:
+            m._prefill_request(*items[0][1:])
+        elif r.n > 1 or (chunk and self._running()):
+            st = m.admit_begin(*items[0])
+            if r.n > 1:
+                st = m.admit_fork(st, kids, r.max_tokens)
+            if chunk and self._running() and st["T"] - st["done"] > chunk:
+                self.prefilling = (r, items[0][0], st)
+                m.admit_step(st, chunk)
+                return False
             m.admit_step(st)
-        except Exception as e:
-            self.prefilling = None
-            if type(e).__name__ == "KvPoolExhausted" and any(v is not None for v in self.slots):
-                self.waiting.appendleft(r)
-                return "wait"
-            self._fail(r, e, done)
-            return "failed"
-        self._place(r, s, st)
-        self._since_sync = self.sync_every               # read the first tokens right away
-        return "ok"
+        else:
+            m._admit(*items[0])
+        for q, it in zip(group, items):
+            self._place(q, it[0], st)
+        self._since_sync = self.sync_every               # read the first token right away (time to first token)
+        return True
+
+    def _admit_waiting(self, done):
+        """free slots take waiting requests (that share the running batch's sampling configuration, on a model with one)"""
+        m = self.model
+        while self.prefilling is None and self.waiting and any(v is None for v in self.slots):
+            free = [i for i, v in enumerate(self.slots) if v is None]
+            cands = self._candidates(free)
+            if not cands:
+                return
+            ready = [r for r in cands if self._encoded(r, done)]
+            if not ready:
+                continue
+            pack = m.plan_pack([r._enc + (r.max_tokens,) for r in ready], free) if self.nslots > 1 and ready[0].n == 1 else []
+            group = [ready[j] for j in pack] if pack else ready[:1]
+            if getattr(m, "_kv_dynamic", False):         # admit only what the block pool can hold
+                if len(group) > 1 and self._pool_gate([c for q in group for c in self._needs(q)]) != "admit":
+                    group = group[:1]
+                r = group[0]
+                needs = self._needs(r)
+                verdict = self._pool_gate(needs)
+                if verdict == "wait":
+                    return
+                if verdict == "never":
+                    self.waiting.remove(r)
+                    # (a single request's count is asked for again, as it always was: the model sees the same calls)
+                    self._fail(r, RuntimeError(f"request needs {sum(needs)} KV positions for its {r.n} samples, more than the block pool "
+                                               f"can hold ({m.kv_stats()})" if r.n > 1 else
+                                               f"request needs {sum(self._needs(r))} KV positions, more than the block pool can hold "
+                                               f"({m.kv_stats()})"), done)
+                    continue
+            items, kids = [], []
+            for r in group:
+                ids, ser, lens = r._enc
+                s = m.pick_slot(free, m._request_idents(ids, ser, lens))      # the slot whose resident prefix matches best
+                free.remove(s)
+                kids = free[:r.n - 1]
+                items.append((s, ids, ser, lens, r.max_tokens))
+                self.waiting.remove(r)
+                if self.mixed:                           # every sequence's own settings
+                    for c, sl in zip(r.outputs, [s] + kids):
+                        self._write_settings(sl, c)
+            try:
+                if not self._start(group, items, kids):
+                    return
+            except Exception as e:
+                self.prefilling = None
+                if type(e).__name__ == "KvPoolExhausted" and self._running():
+                    # the block pool is full (resident-prefix claims of the touched slots were dropped): back to the head of the
+                    # queue, in order, until a running sequence finishes
+                    self.waiting.extendleft(reversed(group))
+                    return
+                for r in group:
+                    self._fail(r, e, done)
 
     # ---- one scheduler iteration ---------------------------------------------------------------------
     def step(self):
@@ -369,19 +364,18 @@ class Engine:
         m = self.model
         done = []
         # (a prompt that is being prefilled in chunks draws its first token with the CURRENT configuration: it counts as running)
-        running = any(s is not None for s in self.slots) or self.prefilling is not None
+        running = self._running() or self.prefilling is not None
         if self.mixed:
-            self._mixed_mode()
-        self._logprobs_mode()
-        self._controls_mode()
+            self._mode("rows", lambda r: r.sampling_key, self.active_key == "rows", lambda on: self._apply_sampling("rows" if on else None))
+        if hasattr(m, "set_logprobs"):
+            self._mode("logprobs", lambda r: r.logprob_k is not None, bool(getattr(m, "_logprobs_on", False)), m.set_logprobs)
+        if hasattr(m, "set_logit_controls"):
+            self._mode("controls", lambda r: r.controls != NO_CONTROLS, bool(getattr(m, "_controls_on", False)), m.set_logit_controls)
         while not self.mixed and not running and self.waiting and self.waiting[0].sampling_key != self.active_key:
             try:
                 self._apply_sampling(self.waiting[0].sampling_key)
             except Exception as e:                       # a configuration the library refuses fails THAT request, not the engine
-                r = self.waiting.popleft()
-                r.error = e
-                self._emit(r, True, "error")
-                done.append(r)
+                self._fail(self.waiting.popleft(), e, done)
         if self.prefilling is not None:                  # a long prompt is on its way in: its next chunk, no other admission meanwhile
             r, s, st = self.prefilling
             try:
@@ -392,110 +386,7 @@ class Engine:
             except Exception as e:
                 self.prefilling = None
                 self._fail(r, e, done)
-        # admission: free slots take waiting requests that share the running batch's sampling configuration
-        while self.prefilling is None and self.waiting and any(v is None for v in self.slots):
-            free = [i for i, v in enumerate(self.slots) if v is None]
-            # requests that share the running batch's sampling configuration may overtake a head of the queue that waits for ANOTHER
-            # one (it joins when the batch has drained) - but only `max_bypass` times, or a steady stream of same-key arrivals
-            # would starve it
-            head = self.waiting[0]
-            if head.n > 1:                               # n samples of one prompt: admitted together, from one prefill
-                if head.n <= len(free):
-                    if self._admit_parent(head, free, done) == "wait":
-                        break
-                    continue
-                if head.bypassed >= self.max_bypass:     # it waits for n free slots; later single requests may pass it, a few times
-                    break
-            if self.mixed:
-                cands = []
-                for q in self.waiting:                   # arrival order; a later request with n > 1 ends the run (it goes first then)
-                    if q.n > 1:
-                        if q is head:
-                            continue
-                        break
-                    cands.append(q)
-                cands = cands[:len(free)]
-                if not cands:
-                    break
-                if head.n > 1:
-                    head.bypassed += len(cands)
-            else:
-                if head.sampling_key != self.active_key and head.bypassed >= self.max_bypass:
-                    break
-                cands = [q for q in self.waiting if q.sampling_key == self.active_key][:len(free)]
-                if not cands:
-                    break
-                if head.sampling_key != self.active_key:
-                    head.bypassed += len(cands)
-            ready = []
-            for r in cands:                              # tokenise / sp-encode once per request
-                if getattr(r, "_enc", None) is None:
-                    try:
-                        r._enc = self._encode(r)
-                        r.prompt_tokens = len(r._enc[0])
-                    except Exception as e:               # a bad request must not take the engine down
-                        self.waiting.remove(r)
-                        r.error = e
-                        self._emit(r, True, "error")
-                        done.append(r)
-                        continue
-                ready.append(r)
-            if not ready:
-                continue
-            pack = m.plan_pack([r._enc + (r.max_tokens,) for r in ready], free) if self.nslots > 1 else []
-            group = [ready[j] for j in pack] if pack else ready[:1]
-            if getattr(m, "_kv_dynamic", False):         # block-paged cache with an oversubscribed pool: admit only what it can hold
-                def need(q):
-                    return m.request_tokens(*q._enc) + q.max_tokens
-                if len(group) > 1 and not m.kv_fits([need(q) for q in group]):
-                    group = group[:1]
-                if not m.kv_fits([need(group[0])]):
-                    if any(v is not None for v in self.slots):
-                        break                            # wait until a running sequence finishes: its blocks become evictable
-                    r = group[0]                         # nothing is running: this request can never fit
-                    self.waiting.remove(r)
-                    r.error = RuntimeError(f"request needs {need(r)} KV positions, more than the block pool can hold ({m.kv_stats()})")
-                    self._emit(r, True, "error")
-                    done.append(r)
-                    continue
-            items = []
-            for r in group:
-                ids, ser, lens = r._enc
-                s = m.pick_slot(free, m._request_idents(ids, ser, lens))      # the slot whose resident prefix matches best
-                free.remove(s)
-                items.append((s, ids, ser, lens, r.max_tokens))
-                self.waiting.remove(r)
-                if self.mixed:                           # the slot's settings, before its first token is drawn
-                    m.set_slot_sampling(s, *r.sampling)
-                    if hasattr(m, "set_slot_controls"):
-                        m.set_slot_controls(s, *r.controls)
-            try:
-                if len(items) > 1:
-                    m._admit_packed(items)               # several short prompts: one packed prefill pass
-                elif self.nslots == 1:
-                    m._prefill_request(*items[0][1:])
-                elif self.prefill_chunk_tokens and any(v is not None for v in self.slots):
-                    st = m.admit_begin(*items[0])         # others are decoding: feed a long prompt in chunks between their steps
-                    if st["T"] - st["done"] > self.prefill_chunk_tokens:
-                        self.prefilling = (group[0], items[0][0], st)
-                        m.admit_step(st, self.prefill_chunk_tokens)
-                        break
-                    m.admit_step(st)
-                else:
-                    m._admit(*items[0])
-            except Exception as e:
-                self.prefilling = None
-                if type(e).__name__ == "KvPoolExhausted" and any(v is not None for v in self.slots):
-                    self.waiting.extendleft(reversed(group))      # the block pool is full (resident-prefix claims of the touched slots were dropped): back to the head
-                    break                                         # of the queue until a running sequence finishes
-                for r in group:
-                    r.error = e
-                    self._emit(r, True, "error")
-                    done.append(r)
-                continue
-            for r, it in zip(group, items):
-                self.slots[it[0]], self.produced[it[0]] = r, 1
-            self._since_sync = self.sync_every          # read the first token right away (time to first token)
+        self._admit_waiting(done)
         live = [s for s in range(self.nslots) if self.slots[s] is not None]
         if not live:
             return done
@@ -533,9 +424,7 @@ class Engine:
                 if self.nslots > 1:
                     B["pos_all"][s] = -1
                 m._slot_idents[s] = []
-                r.error = err
-                self._emit(r, True, "error")
-                done.append(r)
+                self._fail(r, err, done)
             # Each rank reads only ITS OWN sticky status: a peer that arrived late saw no timeout and would keep decoding these
             # slots while this rank hands them to other requests - slot choice and packing would differ between the ranks and every
             # later collective would be mismatched.  So this is fatal for the rank group, not for the running requests only: raise
@@ -736,19 +625,16 @@ class EngineThread:
                 r.on_tokens(r, [], True)
 
     def _reject_invalid(self, new):
-        """validate_sampling on every queued request; the offending ones are answered with an error here and never reach the engine
+        """Engine.check on every queued request; the offending ones are answered with an error here and never reach the engine
         (nor, under tensor parallelism, the followers - add_request raising after control.publish would take every rank down)."""
         ok = []
+        check = getattr(self.engine, "check", validate_sampling)        # (a stand-in engine without check(): the value ranges)
         for kw in new:
             try:
-                validate_sampling(**{k: kw[k] for k in ("max_tokens", "temperature", "top_p", "top_k", "logprobs", "repetition_penalty",
-                                                          "frequency_penalty", "presence_penalty", "min_p", "n", "best_of", "stop")
-                                     if k in kw}, max_logprobs=getattr(self.engine, "max_logprobs", 20))
-                if hasattr(self.engine, "check_request"):       # n > slots, n > 1 / stop on an engine that cannot serve them
-                    self.engine.check_request(kw.get("n"), kw.get("best_of"), kw.get("stop"))
+                check(**{k: kw[k] for k in REQUEST_FIELDS if k in kw})
                 ok.append(kw)
             except (ValueError, TypeError) as e:
-                r = Request(-1, kw.get("prompt"), list(kw.get("timeseries") or []), 1, None, [], kw.get("on_tokens"))
+                r = Request(-1, kw.get("prompt"), list(kw.get("timeseries") or []), kw.get("on_tokens"))
                 r.error, r.finished, r.finish_reason = e, True, "error"
                 holder = kw.get("holder")
                 if holder is not None:
@@ -776,7 +662,7 @@ class EngineThread:
             if self.control is not None:
                 if not new and not self.engine.has_work():
                     continue                       # idle: nothing to announce, the followers keep waiting
-                self.control.publish([{k: v for k, v in kw.items() if k not in ("holder", "on_tokens")} for kw in new])
+                self.control.publish([{k: kw[k] for k in ("prompt", "timeseries") + REQUEST_FIELDS if k in kw} for kw in new])
             for kw in new:
                 holder = kw.pop("holder", None)
                 r = self.engine.add_request(**kw)

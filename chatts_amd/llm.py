@@ -9,38 +9,7 @@ import os
 import numpy as np
 
 
-class SamplingParams:
-    def __init__(self, max_tokens=16, temperature=0.0, top_p=1.0, top_k=-1, seed=None, stop_token_ids=None,
-                 ignore_eos=False, logprobs=None, prompt_logprobs=None, repetition_penalty=1.0, frequency_penalty=0.0,
-                 presence_penalty=0.0, min_p=0.0, n=1, best_of=None, stop=None, include_stop_str_in_output=False, **kw):
-        from .detok import normalize_stop
-        from .engine import validate_controls, validate_n
-        # n: samples per prompt (RequestOutput.outputs[i], i = 0 .. n-1).  Sample i draws with seed + i from a stream of (seed, step)
-        # alone, so it is what an Engine / server request with seed + i generates, and sample 0 is that surface's n = 1 answer.
-        # (LLM.generate serves n = 1 without stop through generate_batch's shared configuration, which with max_num_seqs > 1 folds
-        # the cache slot into the draws: there a sampled n = 1 call is not sample 0 of the n = 2 call - LLM._generate_engine.)
-        # best_of only as None or n.  stop: strings that end a sequence where they appear in its decoded text - the text ends before
-        # the match, or after it with include_stop_str_in_output (chatts_amd/detok.py: the rule)
-        self.n = validate_n(n, best_of)
-        self.best_of = best_of
-        self.stop = normalize_stop(stop)
-        self.include_stop_str_in_output = bool(include_stop_str_in_output)
-        if prompt_logprobs is not None:
-            raise ValueError("prompt_logprobs is not supported (only the logprobs of generated tokens: logprobs=k)")
-        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or logprobs < 0):
-            raise ValueError(f"logprobs must be a non-negative integer, got {logprobs!r}")
-        self.logprobs = logprobs                # k: the chosen token + its k best alternatives per generated token (raw logits)
-        self.max_tokens = int(max_tokens)
-        self.temperature = temperature          # 0 = greedy (this engine's default; the reference's drivers pass 0.2 / 0.5)
-        self.top_p = top_p
-        self.top_k = top_k                      # -1 / 0 = off, like vLLM
-        self.seed = seed
-        self.stop_token_ids = list(stop_token_ids or [])
-        self.ignore_eos = ignore_eos
-        # vLLM's names, defaults and ranges: l / r (l > 0) or l * r for ids of the prompt or the output; l -= f * count and l -= p for
-        # ids of the output; min_p drops ids less probable than min_p x the most probable one (sampled requests only)
-        self.repetition_penalty, self.frequency_penalty, self.presence_penalty, self.min_p = validate_controls(
-            repetition_penalty, frequency_penalty, presence_penalty, min_p)
+from .sampling import REQUEST_FIELDS, SamplingParams, validate_n  # noqa: F401  (SamplingParams: importable from here as before)
 
 
 class Logprob:
@@ -168,6 +137,19 @@ class LLM:
         except Exception:
             pass
 
+    def _requests(self, prompts):
+        """what generate() accepts (a str, a {"prompt", "multi_modal_data": {"timeseries": [...]}} dict, a list of them) ->
+        [(prompt text, list of series)]; ValueError past the limit_mm_per_prompt cap"""
+        out = []
+        for req in [prompts] if isinstance(prompts, (str, dict)) else prompts:
+            if isinstance(req, str):
+                req = {"prompt": req}
+            series = list((req.get("multi_modal_data") or {}).get("timeseries", []))
+            if len(series) > self.limit:
+                raise ValueError(f"At most {self.limit} timeseries may be provided in one prompt, got {len(series)}")
+            out.append((req["prompt"], series))
+        return out
+
     def generate(self, prompts, sampling_params=None, use_tqdm=False):
         if self._tp_group is not None:      # spawned followers run the same call now; all ranks meet inside the exchange kernels
             self._tp_group.call("generate", prompts, sampling_params)
@@ -182,21 +164,14 @@ class LLM:
             self.model.set_logit_controls(False)              # per call too: a default call runs the plain selection
         self.model.set_sampling(sp.temperature or 0.0, max(int(sp.top_k or 0), 0), sp.top_p,
                                 self._seed if sp.seed is None else sp.seed, *controls)
-        if isinstance(prompts, (str, dict)):
-            prompts = [prompts]
         import torch
         reqs, metas = [], []
-        for req in prompts:
-            if isinstance(req, str):
-                req = {"prompt": req}
-            series = list((req.get("multi_modal_data") or {}).get("timeseries", []))
-            if len(series) > self.limit:
-                raise ValueError(f"At most {self.limit} timeseries may be provided in one prompt, got {len(series)}")
-            text, encs, lens = self.processor.splice(req["prompt"], [np.asarray(s, dtype=np.float64) for s in series])
+        for prompt, series in self._requests(prompts):
+            text, encs, lens = self.processor.splice(prompt, [np.asarray(s, dtype=np.float64) for s in series])
             ids = self.processor.tokenizer.encode(text)
             ser = torch.from_numpy(self.processor.pad_stack(encs)) if encs else None
             reqs.append((ids, ser, lens))
-            metas.append((req["prompt"], ids))
+            metas.append((prompt, ids))
         e = self.config.eos_token_id
         eos = None if sp.ignore_eos else ((list(e) if isinstance(e, (list, tuple)) else [e]) + sp.stop_token_ids)
         tok = self.processor.tokenizer
@@ -218,28 +193,18 @@ class LLM:
         do not draw alike.  Hence on such an LLM a sampled call changes its tokens when n > 1 or stop is added (greedy calls do not,
         and neither does any call with max_num_seqs = 1, where there is no slot to fold); Engine and server requests always use the
         per-slot stream, for n = 1 too."""
-        from .engine import Engine, validate_n
+        from .engine import Engine
         m = self.model
         validate_n(sp.n, sp.best_of, max(1, m.max_batch))
-        if isinstance(prompts, (str, dict)):
-            prompts = [prompts]
+        requests = self._requests(prompts)
         if getattr(m, "_sampling_key", None) not in (None, "rows"):
             m.set_sampling(0.0)                    # the engine works with per-slot settings: leave the baked-in configuration
         eng = Engine(m, self.processor, sync_every=8)
         eng.active_key = getattr(m, "_sampling_key", None)
-        kw = dict(max_tokens=sp.max_tokens, temperature=sp.temperature or 0.0, top_p=sp.top_p, top_k=max(int(sp.top_k or 0), 0),
-                  seed=self._seed if sp.seed is None else sp.seed, stop_token_ids=sp.stop_token_ids, ignore_eos=sp.ignore_eos,
-                  logprobs=sp.logprobs, repetition_penalty=sp.repetition_penalty, frequency_penalty=sp.frequency_penalty,
-                  presence_penalty=sp.presence_penalty, min_p=sp.min_p, n=sp.n, stop=sp.stop,
-                  include_stop_str_in_output=sp.include_stop_str_in_output)
-        reqs = []
-        for req in prompts:
-            if isinstance(req, str):
-                req = {"prompt": req}
-            series = list((req.get("multi_modal_data") or {}).get("timeseries", []))
-            if len(series) > self.limit:
-                raise ValueError(f"At most {self.limit} timeseries may be provided in one prompt, got {len(series)}")
-            reqs.append(eng.add_request(req["prompt"], timeseries=series, **kw))
+        kw = {k: getattr(sp, k) for k in REQUEST_FIELDS}
+        if sp.seed is None:
+            kw["seed"] = self._seed
+        reqs = [eng.add_request(prompt, timeseries=series, **kw) for prompt, series in requests]
         eng.run_until_done()
         tok = self.processor.tokenizer
         outs = []

@@ -908,7 +908,7 @@ class ChatTSForCausalLM:
     @staticmethod
     def check_controls(repetition_penalty=None, frequency_penalty=None, presence_penalty=None, min_p=None):
         """-> the four values as floats (None = the default); ValueError outside vLLM's ranges (engine.validate_controls)"""
-        from .engine import validate_controls
+        from .sampling import validate_controls
         return validate_controls(repetition_penalty, frequency_penalty, presence_penalty, min_p)
 
     def _control_buffers(self):

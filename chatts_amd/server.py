@@ -105,10 +105,9 @@ def sampling_from_body(body, default_max_tokens=512, max_num_seqs=None):
             out["include_stop_str_in_output"] = body["include_stop_str_in_output"]
     except (TypeError, ValueError) as e:
         raise ValueError(f"malformed sampling parameter: {e}")
-    from .engine import validate_sampling
+    from .sampling import validate_n, validate_sampling
     validate_sampling(**out)             # ValueError -> 400 (never reaches the engine thread)
     if "n" in out:
-        from .engine import validate_n
         validate_n(out["n"], out.get("best_of"), max_num_seqs)
     return out
 

@@ -495,6 +495,38 @@ def test_engine_thread_answers_what_the_engine_cannot_serve_and_lives_on():
         et.close()
 
 
+def test_engine_thread_answers_controls_and_logprobs_the_model_lacks_and_lives_on():
+    """ForkStub has neither set_slot_controls nor set_logprobs: Engine.add_request raises for such a request, so the engine thread must
+    refuse it BEFORE it is announced (after the publish every rank would go down) - an error on that request, nothing published for
+    it, and the next valid request is served."""
+    class Control:
+        def __init__(self):
+            self.sent = []
+
+        def publish(self, new, stop=False):
+            self.sent.append(list(new))
+    eng, model = _engine(2, _plain)
+    assert not hasattr(model, "set_slot_controls") and not hasattr(model, "set_logprobs")
+    for kw in (dict(min_p=0.1), dict(logprobs=1)):
+        with pytest.raises(ValueError):
+            eng.add_request("P", **kw)
+    control = Control()
+    et = EngineThread(eng, control=control)
+    try:
+        bad1, bad2, good, ev = [], [], [], threading.Event()
+        et.submit(prompt="P", timeseries=[], holder=bad1, frequency_penalty=0.5, on_tokens=lambda r, new, fin: None)
+        et.submit(prompt="P", timeseries=[], holder=bad2, logprobs=2, on_tokens=lambda r, new, fin: None)
+        et.submit(prompt="Q", timeseries=[], holder=good, max_tokens=3, ignore_eos=True, on_tokens=lambda r, new, fin: fin and ev.set())
+        assert ev.wait(10)
+        assert isinstance(bad1[0].error, ValueError) and "does not apply" in str(bad1[0].error) and bad1[0].finish_reason == "error"
+        assert isinstance(bad2[0].error, ValueError) and "does not compute logprobs" in str(bad2[0].error)
+        assert good[0].error is None and good[0].tokens == [_plain(ord("Q"), good[0].sampling[3], s) for s in range(3)]
+        assert et.error is None and et.thread.is_alive()
+        assert [m["prompt"] for new in control.sent for m in new] == ["Q"]        # the refused ones never reached a follower
+    finally:
+        et.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the server on the engine (stub model), the offline surfaces
 # ---------------------------------------------------------------------------------------------------------------------------------
