@@ -125,6 +125,17 @@ class DecoderBuffers(C.Structure):
                 ("kv_dtype", c_int)]      # in the trailing padding: sizeof stays 176
 
 
+SPEC_MAX_DRAFT, SPEC_MAX_ROWS, SPEC_MAX_NGRAM = 8, 9, 8      # CHATTS_SPEC_MAX_* of include/chatts_amd.h
+
+
+class SpecArgs(C.Structure):
+    """ChattsSpecArgs: one speculative (prompt-lookup) decode step, chatts_decoder_spec_step"""
+    _fields_ = [("k", c_int), ("ngram_min", c_int), ("ngram_max", c_int), ("n_splits", c_int), ("skip_propose", c_int),
+                ("hist", c_void_p), ("draft", c_void_p), ("spec_tokens", c_void_p), ("argmax", c_void_p), ("logits", c_void_p),
+                ("pos_dev", c_void_p), ("step_dev", c_void_p), ("token_dev", c_void_p), ("out_tokens", c_void_p),
+                ("out_capacity_dev", c_void_p), ("counters", c_void_p)]
+
+
 # name -> (restype, argtypes); this table IS the list of symbols include/chatts_amd.h declares
 SIGNATURES = {
     "chatts_last_error": (C.c_char_p, []),
@@ -224,6 +235,13 @@ SIGNATURES = {
     "chatts_kv_fork": (c_int, [C.POINTER(KvCache), c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, C.POINTER(c_int32), c_int,
                                c_int, c_int, c_void_p]),
     "chatts_logit_state_fork": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, C.POINTER(c_int32), c_int, c_void_p]),
+    # speculative decoding by prompt lookup (spec_decode.hip, decoder.hip)
+    "chatts_spec_propose": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "chatts_spec_verify": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_void_p]),
+    "chatts_attention_verify": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                        C.POINTER(KvCache), c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "chatts_decoder_spec_step": (c_int, [c_void_p, C.POINTER(SpecArgs), c_void_p]),
     # tensor-parallel exchange (tp.hip)
     "chatts_tp_buffer_bytes": (c_size_t, [c_int, c_int64]),
     "chatts_tp_buffer_bytes_bulk": (c_size_t, [c_int, c_int64, c_int64]),

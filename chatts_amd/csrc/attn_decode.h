@@ -426,9 +426,9 @@ __device__ __forceinline__ void attn_decode_wave(const AttnParams& p, const int 
 // o_s[d] loads are in flight per thread: no LDS, no barrier.
 // One wave's half of a head: d = half * 64 + lane (two waves per head).  The partials of head hq are part_o / part_ml rows
 // base .. base + n_splits - 1 (global workspace: base = (seq * n_q + hq) * n_splits; LDS of the workgroup form: its local head index).
-__device__ __forceinline__ void attn_combine_wave(const AttnParams& p, const int hq, const int seq, const int d, const int lane,
-                                                  const float* part_o, const float* part_ml, const size_t base) {
-  const int pos = p.pos0_dev ? p.pos0_dev[seq] : p.pos0;
+// (attn_combine_wave_at: the same with the row's position given by the caller - the verify attention's rows share one pos_dev)
+__device__ __forceinline__ void attn_combine_wave_at(const AttnParams& p, const int hq, const int seq, const int d, const int lane,
+                                                     const float* part_o, const float* part_ml, const size_t base, const int pos) {
   const int ntiles = pos < 0 ? 0 : pos / kDTile + 1;         // parked slot: no partials exist, the row is written as zeros
   const int ns = ntiles < p.n_splits ? ntiles : p.n_splits;
   // every load of this wave is requested before the first use (round 5): (m, l) of the slots and all <= 64 partial rows of this lane's
@@ -461,6 +461,10 @@ __device__ __forceinline__ void attn_combine_wave(const AttnParams& p, const int
   } else {
     p.out[oi] = v;
   }
+}
+__device__ __forceinline__ void attn_combine_wave(const AttnParams& p, const int hq, const int seq, const int d, const int lane,
+                                                  const float* part_o, const float* part_ml, const size_t base) {
+  attn_combine_wave_at(p, hq, seq, d, lane, part_o, part_ml, base, p.pos0_dev ? p.pos0_dev[seq] : p.pos0);
 }
 
 }  // namespace chatts

@@ -20,6 +20,10 @@ int attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0, const i
                    uint16_t* out_hi, uint16_t* out_lo, int n_splits, void* workspace, size_t workspace_bytes, chatts_stream_t stream);
 int launch_split_bf16x2(const float* x, int m, int k, int ldx, uint16_t* hi, uint16_t* lo, int ldp, hipStream_t s);
 size_t gemm_workspace(int m, int n, int k);
+int attention_verify_impl(const float* qkv_raw, int rows, int n_q, int n_kv, const float* q_norm_w, const float* k_norm_w, float norm_eps,
+                          const float* cos_tab, const float* sin_tab, const int32_t* pos_dev, const ChattsKvCache* cache, float* out,
+                          uint16_t* out_hi, uint16_t* out_lo, int n_splits, void* workspace, size_t workspace_bytes,
+                          chatts_stream_t stream);
 }  // namespace chatts
 
 using namespace chatts;
@@ -45,6 +49,8 @@ struct ChattsDecoder {
   bool prefill_fp8 = false; // SPEED MODE (chatts_decoder_set_prefill_fp8): prefill chunks of >= 16 rows multiply fp8 x fp8 (gemm_fp8.hip)
   bool fuse_tp = false;     // set by chatts_decoder_decode_step: the M == 1 o_proj / down_proj GEMVs carry the exchange in their own launch
   bool tp_fused = false;    // ... and whether the last layer part's projection did (otherwise the caller launches chatts_allreduce)
+  int spec_rows = 0;        // set by chatts_decoder_spec_step: the `batch` rows of layer_part_batched are consecutive positions of the
+                            // SELECTED sequence (verify attention on its cache), not one token of each of the cache slots 0 .. batch - 1
 };
 
 static int64_t embed_rows(const ChattsDecoder* d) { return d->cfg.embed_rows > 0 ? d->cfg.embed_rows : d->cfg.vocab_local; }
@@ -675,7 +681,7 @@ extern "C" int chatts_decoder_layer_part_batched(ChattsDecoder* d, int layer, in
                                                  const int32_t* pos_dev, int n_splits, chatts_stream_t stream) {
   CHATTS_REQUIRE(d && layer >= 0 && layer < d->cfg.n_layers && (part == 0 || part == 1) && pos_dev, CHATTS_E_BADARG,
                  "decoder_layer_part_batched: bad arguments");
-  const int maxb = d->b.max_batch > 0 ? d->b.max_batch : 1;
+  const int maxb = d->spec_rows > 0 ? d->spec_rows : (d->b.max_batch > 0 ? d->b.max_batch : 1);      // (max_batch guards cache slots)
   CHATTS_REQUIRE(batch >= 1 && batch <= maxb && batch <= d->b.t_max, CHATTS_E_SHAPE,
                  "decoder_layer_part_batched: batch %d exceeds max_batch %d", batch, maxb);
   StageRange stage(part == 0 ? "chatts.layer.attn" : "chatts.layer.mlp");
@@ -694,9 +700,13 @@ extern "C" int chatts_decoder_layer_part_batched(ChattsDecoder* d, int layer, in
     la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
     if ((rc = norm_into(d, lw.input_norm, &la, stream)) != 0) return rc;
     if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-    ChattsKvCache kc = layer_cache(d, layer, 0);
+    ChattsKvCache kc = layer_cache(d, layer, d->spec_rows > 0 ? d->cur_seq : 0);
     const bool attn_planes = planes_path(d, batch, c.n_q * kHeadDim, lw.o8 != nullptr);   // the combine writes o_proj's operand format
-    if ((rc = attention_decode_batched_impl(d->b.qkv, batch, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, 0,
+    if (d->spec_rows > 0) {
+      if ((rc = attention_verify_impl(d->b.qkv, batch, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos_dev,
+                                      &kc, d->b.attn, attn_planes ? d->b.planes_hi : nullptr, attn_planes ? d->b.planes_lo : nullptr,
+                                      n_splits, d->b.workspace, d->b.workspace_bytes, stream)) != 0) return rc;
+    } else if ((rc = attention_decode_batched_impl(d->b.qkv, batch, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, 0,
                                             pos_dev, &kc, seq_stride(d), d->b.attn, attn_planes ? d->b.planes_hi : nullptr,
                                             attn_planes ? d->b.planes_lo : nullptr, n_splits, d->b.workspace, d->b.workspace_bytes,
                                             stream)) != 0) return rc;
@@ -748,7 +758,7 @@ extern "C" int chatts_decoder_layer_part_batched(ChattsDecoder* d, int layer, in
 // batched step (compute_logits for a batch, chatts_vllm.py:603-610).  M = batch weight-streaming GEMM on this rank's vocabulary slice.
 extern "C" int chatts_decoder_logits_batched(ChattsDecoder* d, int batch, float* logits_all, chatts_stream_t stream) {
   CHATTS_REQUIRE(d && logits_all, CHATTS_E_BADARG, "decoder_logits_batched: null argument");
-  const int maxb = d->b.max_batch > 0 ? d->b.max_batch : 1;
+  const int maxb = d->spec_rows > 0 ? d->spec_rows : (d->b.max_batch > 0 ? d->b.max_batch : 1);
   CHATTS_REQUIRE(batch >= 1 && batch <= maxb && batch <= d->b.t_max, CHATTS_E_SHAPE, "decoder_logits_batched: batch %d exceeds max_batch %d",
                  batch, maxb);
   const ChattsDecoderConfig& c = d->cfg;
@@ -1046,4 +1056,54 @@ extern "C" int chatts_decoder_decode_step(ChattsDecoder* d, int32_t* pos_dev, in
   if ((rc = chatts_decoder_select_tokens(d, d->b.logits, 1, d->cfg.vocab_local, token_dev, token_logit_dev, out_tokens, 0, step_dev,
                                          pos_dev, 0, nullptr, stream)) != 0) return rc;
   return chatts_embed_token(token_dev, d->w.embed, embed_offset(d), embed_rows(d), d->cfg.hidden, d->b.x, stream);
+}
+
+// One speculative step (spec_decode.hip; include/chatts_amd.h): R = k + 1 rows of the selected sequence - its last chosen token and k
+// drafts from its own history - through the batched-row projections in ONE pass over the weights, the verify attention in place of
+// the per-slot attention, then per-row argmax and the accept / rollback kernel.  Device-driven like the plain step: capture once, replay.
+extern "C" int chatts_decoder_spec_step(ChattsDecoder* d, const ChattsSpecArgs* a, chatts_stream_t stream) {
+  CHATTS_REQUIRE(d && a, CHATTS_E_BADARG, "decoder_spec_step: null argument");
+  CHATTS_REQUIRE(a->hist && a->draft && a->spec_tokens && a->argmax && a->logits && a->pos_dev && a->step_dev && a->token_dev &&
+                     a->out_tokens && a->out_capacity_dev && a->counters, CHATTS_E_BADARG, "decoder_spec_step: null pointer in the arguments");
+  CHATTS_REQUIRE(a->k >= 1 && a->k <= CHATTS_SPEC_MAX_DRAFT, CHATTS_E_BADARG, "decoder_spec_step: k = %d must be in 1..%d", a->k,
+                 CHATTS_SPEC_MAX_DRAFT);
+  CHATTS_REQUIRE(a->ngram_min >= 1 && a->ngram_max >= a->ngram_min && a->ngram_max <= CHATTS_SPEC_MAX_NGRAM, CHATTS_E_BADARG,
+                 "decoder_spec_step: n-gram sizes %d..%d must satisfy 1 <= min <= max <= %d", a->ngram_min, a->ngram_max, CHATTS_SPEC_MAX_NGRAM);
+  CHATTS_REQUIRE(d->cfg.tp_world <= 1, CHATTS_E_BADARG, "decoder_spec_step: tensor_parallel_size 1 only (tp_world = %d)", d->cfg.tp_world);
+  CHATTS_REQUIRE(!d->sampling && !d->controls, CHATTS_E_BADARG,
+                 "decoder_spec_step: greedy decoding only (a sampler or logit controls are set on the decoder)");
+  const ChattsDecoderConfig& c = d->cfg;
+  const int R = a->k + 1;
+  CHATTS_REQUIRE(R <= d->b.t_max && R < c.max_ctx, CHATTS_E_SHAPE, "decoder_spec_step: %d rows exceed the buffers (%d) or the context", R,
+                 d->b.t_max);
+  int ns = a->n_splits < 1 ? 1 : (a->n_splits > 64 ? 64 : a->n_splits);
+  while (ns > 1 && chatts_attn_workspace(R, c.n_q, ns) > d->b.workspace_bytes) ns /= 2;      // fewer, longer tile slots: the partials must fit
+  CHATTS_REQUIRE(d->b.workspace && chatts_attn_workspace(R, c.n_q, ns) <= d->b.workspace_bytes, CHATTS_E_WORKSPACE,
+                 "decoder_spec_step: the workspace does not hold the attention partials of %d rows", R);
+  StageRange stage("chatts.spec_step");
+  int rc;
+  const int64_t vocab = embed_offset(d) + embed_rows(d);
+  if (!a->skip_propose &&
+      (rc = chatts_spec_propose(a->pos_dev, a->hist, c.max_ctx, a->k, a->ngram_min, a->ngram_max, vocab, a->draft, a->spec_tokens, stream)) != 0)
+    return rc;
+  if ((rc = chatts_embed_token_batched(a->spec_tokens, R, d->w.embed, embed_offset(d), embed_rows(d), c.hidden, d->b.x, stream)) != 0) return rc;
+  d->chain = true;
+  d->normed = false; d->normed_q = false;
+  d->spec_rows = R;
+  rc = CHATTS_OK;
+  for (int l = 0; l < c.n_layers && rc == CHATTS_OK; ++l) {
+    rc = chatts_decoder_layer_part_batched(d, l, 0, R, a->pos_dev, ns, stream);
+    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part_batched(d, l, 1, R, a->pos_dev, ns, stream);
+  }
+  d->chain = false;
+  if (rc == CHATTS_OK) rc = chatts_decoder_logits_batched(d, R, a->logits, stream);
+  d->spec_rows = 0;
+  d->normed = false; d->normed_q = false;
+  if (rc) return rc;
+  // per-row argmax without side effects (the split-K / attention workspace is idle here)
+  if ((rc = chatts::argmax_batched_scratch(a->logits, R, c.vocab_local, c.vocab_local, c.vocab_offset, a->argmax, nullptr, nullptr, 0, nullptr,
+                                           nullptr, 0, d->b.workspace, d->b.workspace_bytes, reinterpret_cast<hipStream_t>(stream))) != 0)
+    return rc;
+  return chatts_spec_verify(a->argmax, a->draft, a->k, vocab, a->pos_dev, a->step_dev, a->token_dev, a->out_tokens, a->out_capacity_dev,
+                            a->hist, c.max_ctx, a->counters, stream);
 }

@@ -255,7 +255,9 @@ class Engine:
         """KV positions of r's sequences (n > 1: the shared whole prompt blocks are counted once, with sample 0)"""
         m = self.model
         T = m.request_tokens(*r._enc)
-        return [T + r.max_tokens] + ([m.fork_tokens(T, r.max_tokens)] * (r.n - 1) if r.n > 1 else [])
+        spec = getattr(m, "spec_reserve", None)          # a speculating request reserves k more positions (modeling._prefill_request)
+        extra = spec(T, r.max_tokens) if spec is not None and self.nslots == 1 else 0
+        return [T + r.max_tokens + extra] + ([m.fork_tokens(T, r.max_tokens)] * (r.n - 1) if r.n > 1 else [])
 
     def _pool_gate(self, needs):
         """block-paged cache with an oversubscribed pool -> "admit"; "wait" until a running sequence finishes (its blocks become
@@ -397,6 +399,12 @@ class Engine:
                 return done
         if self.nslots == 1:
             m.decode_step()
+            if getattr(m, "_spec_request", False):
+                # upper bound of the tokens on the device (a speculative step emits at most k + 1): once the request MAY be complete,
+                # read the device before the next step - a step after the last token would be a pass over the weights for nothing
+                self._spec_most = max(getattr(self, "_spec_most", 0), self.produced[0]) + m._spec_now["k"] + 1
+                if self._spec_most >= self.slots[0].max_tokens:
+                    self._since_sync = self.sync_every
         else:
             m.batched_step()
         for s in live:
@@ -410,6 +418,10 @@ class Engine:
         m, B = self.model, self.model.buf
         done = []
         self._since_sync = 0
+        if self.nslots == 1 and self.slots[0] is not None and getattr(m, "_spec_request", False):
+            # speculative steps emit 1 .. k + 1 tokens: the count kept here (one per step) is a lower bound, the device's counter rules
+            self.produced[0] = m._spec_produced(self.produced[0], self.slots[0].max_tokens)
+            self._spec_most = self.produced[0]
         toks_all = B["out_tokens_all"].cpu() if self.nslots > 1 else B["out_tokens"][None].cpu()
         tp = getattr(m, "_tp", None)
         if tp is not None and tp.status():

@@ -74,12 +74,17 @@ def _build_llm(model, kw):
 class LLM:
     def __init__(self, model, tensor_parallel_size=1, max_model_len=6000, limit_mm_per_prompt=None,
                  trust_remote_code=True, gpu_memory_utilization=None, seed=0, tokenizer=None, comm=None,
-                 max_num_seqs=1, block_size=None, num_gpu_blocks_override=None, kv_cache_dtype=None, max_logprobs=20, **kw):
+                 max_num_seqs=1, block_size=None, num_gpu_blocks_override=None, kv_cache_dtype=None, max_logprobs=20,
+                 speculative_config=None, **kw):
         from .config import PRESETS, ChatTSConfig, preset
         from .modeling import ChatTSForCausalLM
         from .processing import ChatTSProcessor
         from .tp import Comm, LocalComm
         self._tp_group = None
+        # speculative_config (vLLM's name and dict): {"method": "ngram", "num_speculative_tokens": k, "prompt_lookup_max": 3,
+        # "prompt_lookup_min": 1} - prompt-lookup speculative decoding for greedy requests; needs tensor_parallel_size 1, max_num_seqs 1
+        from .spec import parse_speculative_config
+        parse_speculative_config(speculative_config, tensor_parallel_size, max_num_seqs)      # ValueError before any device / worker
         if tensor_parallel_size > 1 and comm is None and "WORLD_SIZE" not in os.environ:
             import torch.distributed as dist
             if not dist.is_initialized():
@@ -107,7 +112,7 @@ class LLM:
         # kv_cache_dtype (vLLM's name): None / "auto" = the float32 KV cache, "fp16" = the half-size speed mode (ChatTSForCausalLM)
         mk = dict(comm=comm, max_ctx=max_model_len, max_prefill_tokens=min(2048, max_model_len),
                   max_batch=max(1, int(max_num_seqs)), kv_block_size=block_size, kv_pool_blocks=num_gpu_blocks_override,
-                  kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs)
+                  kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs, speculative_config=speculative_config)
         if isinstance(model, ChatTSConfig):
             self.model = ChatTSForCausalLM.from_synthetic(model, seed=seed, **mk)
         elif isinstance(model, str) and model in PRESETS:

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, prefix_cache, synth
 from .config import ChatTSConfig, preset
+from .spec import parse_speculative_config
 from .tp import Comm, LocalComm, ShardPlan
 from .ts_encoder import TimeSeriesEmbedding
 
@@ -122,8 +123,17 @@ class ChatTSForCausalLM:
 
     def __init__(self, config, device="cuda", comm=None, max_ctx=2048, max_prefill_tokens=2048, use_graph=True,
                  max_batch=1, weight_format="bf16", use_p2p=True, enable_prefix_caching=True, kv_block_size=None,
-                 kv_pool_blocks=None, precision=None, prefill_tiled_weights=None, kv_cache_dtype=None, max_logprobs=20):
+                 kv_pool_blocks=None, precision=None, prefill_tiled_weights=None, kv_cache_dtype=None, max_logprobs=20,
+                 speculative_config=None):
         kv_name = kv_cache_dtype_name(kv_cache_dtype)       # (checked before anything touches the device)
+        # speculative_config (vLLM's dict, {"method": "ngram", "num_speculative_tokens": k, "prompt_lookup_max": 3, "prompt_lookup_min": 1}):
+        # prompt-lookup speculative decoding for greedy requests of the single-sequence path (chatts_amd/spec.py, csrc/spec_decode.hip).
+        # None = off: no buffer, no launch and no graph of the feature exists.
+        self._spec_cfg = parse_speculative_config(speculative_config, 1 if comm is None else comm.world, max_batch)
+        self._spec_call = None                   # the configuration of ONE generate() call (HF's prompt_lookup_num_tokens)
+        self._spec_active = False                # the running request takes the speculative step
+        self._spec_request = False               # ... or did when it started: host token counts are lower bounds, the device step counter rules
+        self._spec_graphs = {}                   # (k, ngram_min, ngram_max) -> captured speculative step
         if not 0 <= int(max_logprobs) <= _lib.LOGPROBS_MAX_K:
             raise ValueError(f"max_logprobs={max_logprobs} must be in 0..{_lib.LOGPROBS_MAX_K}")
         if not torch.cuda.is_available():
@@ -412,10 +422,17 @@ class ChatTSForCausalLM:
             ws_bytes = max(ws_bytes, int(lib.chatts_linear_workspace(m, plan.vocab, H)))
         ws_bytes = max(ws_bytes, int(lib.chatts_attn_workspace(self.max_batch, plan.nq, self.n_splits)) + 256)
         ws_bytes = max(ws_bytes, int(lib.chatts_logprobs_workspace(max(1, self.max_batch), self.max_logprobs)))
+        if self._spec_cfg is not None:           # the speculative step: lm_head for 2 .. 9 rows, attention partials of 9 rows
+            ws_bytes = max(ws_bytes, self._spec_workspace_bytes())
         # the prefill attention's K / V planes (kv_planes_kernel: 32 KB per (kv head, 32-key tile)) for a sequence of max_ctx positions:
         # with the workspace sized for them the planes kernel is taken at EVERY chunk position, so the same prompt never changes
         # kernel (and summation order) with where a chunk starts
         return max(ws_bytes, ((self.max_ctx + 31) // 32) * plan.nkv * 4 * 32 * self.config.head_dim * 2 + 256)
+
+    def _spec_workspace_bytes(self):
+        lib, plan, H = self.lib, self.plan, self.config.hidden_size
+        need = max(int(lib.chatts_linear_workspace(m, plan.vocab, H)) for m in range(2, _lib.SPEC_MAX_ROWS + 1))
+        return max(need, int(lib.chatts_attn_workspace(_lib.SPEC_MAX_ROWS, plan.nq, min(self.n_splits, 16))) + 256)
 
     def _alloc_buffers(self, ws_bytes):
         cfg, plan, dev = self.config, self.plan, self.device
@@ -813,6 +830,7 @@ class ChatTSForCausalLM:
     def reset(self):
         self.buf["pos"].zero_()
         self.buf["step"].zero_()
+        self._spec_active = self._spec_request = False      # (a sequence set up by hand - prefill(), _first_token() - takes the plain step)
 
     def prefill(self, inputs_embeds, pos0=0, for_next_token=False):
         """Chunked prefill of [T,H] embeddings starting at cache position pos0; leaves the last chunk in x and returns the
@@ -1127,7 +1145,13 @@ class ChatTSForCausalLM:
 
     def decode_step(self):
         """One token.  A hipGraph of the whole step (captured on first use) is replayed - under tensor parallelism too, when the
-        peer-to-peer exchange is attached (its collectives are ordinary kernels with device-resident epochs)."""
+        peer-to-peer exchange is attached (its collectives are ordinary kernels with device-resident epochs).  A request that was
+        admitted for speculative decoding (speculative_config) takes the speculative step instead: 1 .. k + 1 tokens."""
+        if self._spec_active:
+            if self._spec_allowed():
+                return self._spec_decode_step()
+            self._spec_active = False            # a sampler / logprobs / controls were switched on under the request: plain steps from here,
+            self._load_token_embedding()         # which start from the current token's embedding in x[0]
         if self.graph_capturable():
             if self._graph is None:
                 self._capture()
@@ -1171,6 +1195,119 @@ class ChatTSForCausalLM:
         """forget the captured decode steps: the next one captures again (after a change of what a step launches)"""
         self._graph = None
         self._graph_batched = None
+        self._spec_graphs = {}
+
+    # ---------------------------------------------------------------------------------------------
+    # speculative decoding by prompt lookup (csrc/spec_decode.hip, chatts_decoder_spec_step; greedy, one sequence, TP = 1)
+    # ---------------------------------------------------------------------------------------------
+    def _spec_buffers(self):
+        """device state of the speculative step, allocated on first use: token history, drafts, the rows' logits, counters"""
+        B = self.buf
+        if "spec_hist" not in B:
+            dev, R = self.device, _lib.SPEC_MAX_ROWS
+            B["spec_hist"] = torch.zeros(self.max_ctx, dtype=torch.int32, device=dev)
+            B["spec_draft"] = torch.full((R - 1,), -1, dtype=torch.int32, device=dev)
+            B["spec_tokens"] = torch.zeros(R, dtype=torch.int64, device=dev)
+            B["spec_argmax"] = torch.zeros(R, dtype=torch.int64, device=dev)
+            B["spec_logits"] = torch.zeros((R, self.plan.vocab), dtype=torch.float32, device=dev)
+            B["spec_cap"] = torch.zeros(1, dtype=torch.int32, device=dev)
+            B["spec_counters"] = torch.zeros(4, dtype=torch.int64, device=dev)
+        return B
+
+    def _spec_allowed(self):
+        """may the selected sequence take the speculative step now?  Greedy, no logit controls, no logprobs, one sequence, TP = 1."""
+        return (self.plan.world == 1 and self.max_batch == 1 and getattr(self, "_sampling_key", None) is None
+                and not self._controls_on and not self._logprobs_on)
+
+    def _spec_config_for(self, T, max_new_tokens):
+        """-> the speculative configuration the request of T prompt positions will run with, or None (plain steps)"""
+        cfg = self._spec_call or self._spec_cfg
+        if cfg is None or not self._spec_allowed():
+            return None
+        R = cfg["k"] + 1
+        if T + max_new_tokens + cfg["k"] > self.max_ctx or R > self.t_max:     # the k + 1 rows of a step must fit behind the last token
+            return None
+        if self._spec_cfg is None and self.buf["ws"].numel() < self._spec_workspace_bytes():
+            # per-call configuration on a model whose workspace was sized without the feature and cannot hold a step's scratch
+            import warnings
+            warnings.warn("prompt_lookup_num_tokens is ignored: this model's workspace was sized without speculative decoding and is too "
+                          "small for it; build the model with speculative_config=... to use it")
+            return None
+        return cfg
+
+    def spec_reserve(self, T, max_new_tokens):
+        """KV positions a request of T prompt positions needs BEYOND T + max_new_tokens: the k rows a speculative step writes past the
+        last token when the request would speculate under the model's own configuration, else 0 (the engine's pool gate asks)"""
+        if self._spec_cfg is None or not self._spec_allowed():
+            return 0
+        k = self._spec_cfg["k"]
+        return k if T + max_new_tokens + k <= self.max_ctx and k + 1 <= self.t_max else 0
+
+    def _spec_begin(self, cfg, full, T, max_new_tokens):
+        """after the prefill and the first token of a request: its history and output capacity go to the device"""
+        B = self._spec_buffers()
+        B["spec_hist"][:T].copy_(torch.tensor(full, dtype=torch.int32))
+        B["spec_hist"][T:T + 1].copy_(B["token"])
+        B["spec_cap"].fill_(int(max_new_tokens))
+        self._spec_now = cfg
+        self._spec_active = self._spec_request = True
+
+    def _spec_args(self, cfg, skip_propose):
+        B = self._spec_buffers()
+        return _lib.SpecArgs(k=cfg["k"], ngram_min=cfg["ngram_min"], ngram_max=cfg["ngram_max"], n_splits=self.n_splits,
+                             skip_propose=int(skip_propose), hist=_lib.ptr(B["spec_hist"]), draft=_lib.ptr(B["spec_draft"]),
+                             spec_tokens=_lib.ptr(B["spec_tokens"]), argmax=_lib.ptr(B["spec_argmax"]), logits=_lib.ptr(B["spec_logits"]),
+                             pos_dev=_lib.ptr(B["pos"]), step_dev=_lib.ptr(B["step"]), token_dev=_lib.ptr(B["token"]),
+                             out_tokens=_lib.ptr(B["out_tokens"]), out_capacity_dev=_lib.ptr(B["spec_cap"]),
+                             counters=_lib.ptr(B["spec_counters"]))
+
+    def _spec_propose(self):
+        """The proposer on its own (chatts_spec_propose): drafts and the step's input tokens from the sequence's history.  The eager
+        step calls it through this method, so a test can put another proposer in its place."""
+        B, cfg = self._spec_buffers(), self._spec_now
+        _lib.check(self.lib.chatts_spec_propose(_lib.ptr(B["pos"]), _lib.ptr(B["spec_hist"]), self.max_ctx, cfg["k"], cfg["ngram_min"],
+                                                cfg["ngram_max"], self.config.vocab_size, _lib.ptr(B["spec_draft"]),
+                                                _lib.ptr(B["spec_tokens"]), _lib.stream_ptr()))
+
+    def _spec_step_eager(self, propose_in_step=False):
+        """propose_in_step: chatts_decoder_spec_step launches the proposer itself (skip_propose = 0) instead of this object's
+        _spec_propose: the same kernel on the same buffers"""
+        if not propose_in_step:
+            self._spec_propose()
+        args = self._spec_args(self._spec_now, not propose_in_step)
+        _lib.check(self.lib.chatts_decoder_spec_step(self._decoder, C.byref(args), _lib.stream_ptr()))
+
+    def _spec_decode_step(self):
+        """One speculative step of the running request: the captured graph of (propose, R-row pass, argmax, verify), or the same
+        launches eagerly (use_graph=False)."""
+        if not self.graph_capturable():
+            return self._spec_step_eager()
+        cfg = self._spec_now
+        key = (cfg["k"], cfg["ngram_min"], cfg["ngram_max"])
+        g = self._spec_graphs.get(key)
+        if g is None:
+            keys = ("pos", "step", "token", "out_tokens", "x", "spec_hist", "spec_draft", "spec_tokens", "spec_counters")
+            g = self._spec_graphs[key] = self._capture_graph(self._spec_step_eager, keys)
+        g.replay()
+
+    def _spec_produced(self, produced, limit):
+        """host token count of the running request at a sync point: with speculative steps the count kept by the host (one per
+        step) is a lower bound and the device's step counter is the truth; never more than `limit` (max_new_tokens)"""
+        if not self._spec_request:
+            return produced
+        return min(max(produced, int(self.buf["step"][0])), limit)
+
+    @property
+    def spec_stats(self):
+        """speculative decoding counters since the model was built (or spec_stats_reset): steps, drafted (valid draft tokens),
+        accepted (drafts that were emitted), emitted (tokens the speculative steps produced)"""
+        if "spec_counters" not in self.buf:
+            return {"steps": 0, "drafted": 0, "accepted": 0, "emitted": 0}
+        return dict(zip(("steps", "drafted", "accepted", "emitted"), self.buf["spec_counters"].tolist()))
+
+    def spec_stats_reset(self):
+        if "spec_counters" in self.buf:
+            self.buf["spec_counters"].zero_()
 
     # ---------------------------------------------------------------------------------------------
     # batched decode / continuous batching (SURVEY.md section 8f item 1; TP = 1)
@@ -1676,13 +1813,23 @@ class ChatTSForCausalLM:
         eos = _eos_set(eos_token_id)
         produced = 1
         toks = None
+        steps = 1
+        most = 1                     # speculative request: upper bound of the tokens on the device (a step emits at most k + 1)
         while produced < max_new_tokens:
             self.decode_step()
             produced += 1
-            if eos and (produced % sync_every == 0):
+            steps += 1
+            if self._spec_request:
+                # a speculative step emits 1 .. k + 1 tokens: ask the device at the usual sync points, and whenever the request MAY be
+                # complete - a step launched after the last token would be a whole pass over the weights for nothing
+                most += self._spec_now["k"] + 1
+                if steps % sync_every == 0 or most >= max_new_tokens:
+                    produced = most = self._spec_produced(produced, max_new_tokens)
+            if eos and (steps % sync_every == 0):
                 toks = self.buf["out_tokens"][:produced].tolist()
                 if any(t in eos for t in toks):
                     break
+        produced = self._spec_produced(produced, max_new_tokens)
         toks = self.buf["out_tokens"][:produced].tolist()
         self._check_exchange()
         toks = toks[:_eos_end(toks, eos)]
@@ -1711,6 +1858,7 @@ class ChatTSForCausalLM:
         produced, sent = 1, 0
         while True:
             if produced - sent >= chunk or produced >= max_new_tokens:
+                produced = self._spec_produced(produced, max_new_tokens)
                 toks = self.buf["out_tokens"][sent:produced].tolist()
                 self._check_exchange()
                 end = _eos_end(toks, eos)
@@ -1726,9 +1874,11 @@ class ChatTSForCausalLM:
 
     def _prefill_request(self, ids, series, lengths, max_new_tokens):
         """TS encode + merge + prefill + first token of one request on the single-sequence path -> prompt length T."""
-        T, emb, idents, _, _ = self._prepare_request(ids, series, lengths, max_new_tokens)
+        T, emb, idents, _, lengths = self._prepare_request(ids, series, lengths, max_new_tokens)
+        self._spec_active = self._spec_request = False
+        spec = self._spec_config_for(T, max_new_tokens) if (self._spec_cfg or self._spec_call) else None
         self._controls_admit(0, ids)
-        self.reserve_kv(0, T + max_new_tokens, idents)
+        self.reserve_kv(0, T + max_new_tokens + (spec["k"] if spec else 0), idents)     # (a speculative step writes k rows past the token)
         n0 = self._reuse_prefix(0, idents, T)
         self._slot_idents[0] = idents
         self.prefix_stats["tokens_prefilled"] += T - n0
@@ -1736,18 +1886,43 @@ class ChatTSForCausalLM:
         last = self.prefill(emb[n0:], n0, for_next_token=True)
         self.buf["pos"].fill_(T)
         self._first_token(last)
+        if spec:
+            self._spec_begin(spec, self.expand_input_ids(list(ids), self._patch_counts(lengths or [])), T, max_new_tokens)
         return T
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, timeseries=None, max_new_tokens=64, max_length=None,
                  streamer=None, eos_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None,
-                 seed=0, synced_gpus=False, valid_lengths=None, repetition_penalty=None, min_p=None, **kw):
+                 seed=0, synced_gpus=False, valid_lengths=None, repetition_penalty=None, min_p=None, prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=None, **kw):
         """model.generate(**inputs, max_new_tokens=...) -> LongTensor [B, T_in + new] (README.md:102, demo_hf.ipynb
         cell 5).  Greedy unless do_sample=True, like HF; with do_sample the HF GenerationConfig defaults apply to what is
         not given (temperature 1.0, top_k 50, top_p 1.0; the reference's deepspeed driver passes temperature=0.2,
         inference_tsmllm_deepspeed.py:95-100).  Rows start with the un-expanded input_ids; shorter rows are
         right-padded with pad_token_id.  A flat `timeseries` tensor is consumed across the batch in prompt order.
-        repetition_penalty and min_p have HF's meaning: the penalty applies with and without do_sample, min_p only with it."""
+        repetition_penalty and min_p have HF's meaning: the penalty applies with and without do_sample, min_p only with it.
+        prompt_lookup_num_tokens=k (HF's name; max_matching_ngram_size=n, default 2 like HF): prompt-lookup speculative decoding for
+        THIS call, when it is greedy and has no repetition penalty; otherwise the two are ignored with a warning."""
+        self._spec_call = None
+        if prompt_lookup_num_tokens is not None:
+            greedy = not do_sample and (repetition_penalty is None or float(repetition_penalty) == 1.0)
+            call = parse_speculative_config({"method": "ngram", "num_speculative_tokens": prompt_lookup_num_tokens,
+                                             "prompt_lookup_max": 2 if max_matching_ngram_size is None else max_matching_ngram_size,
+                                             "prompt_lookup_min": 1}, self.plan.world, self.max_batch)
+            if greedy:
+                self._spec_call = call
+            else:
+                import warnings
+                warnings.warn("prompt_lookup_num_tokens is ignored: speculative decoding serves greedy requests without a repetition "
+                              "penalty only")
+        try:
+            return self._generate(input_ids, attention_mask, timeseries, max_new_tokens, max_length, streamer, eos_token_id, do_sample,
+                                  temperature, top_k, top_p, seed, valid_lengths, repetition_penalty, min_p)
+        finally:
+            self._spec_call = None
+
+    def _generate(self, input_ids, attention_mask, timeseries, max_new_tokens, max_length, streamer, eos_token_id, do_sample,
+                  temperature, top_k, top_p, seed, valid_lengths, repetition_penalty, min_p):
         if do_sample:
             self.set_sampling(1.0 if temperature is None else temperature, 50 if top_k is None else top_k,
                               1.0 if top_p is None else top_p, seed, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,

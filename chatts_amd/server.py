@@ -358,7 +358,8 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
 
 def build_server(model, tensor_parallel_size=1, max_model_len=6000, max_num_seqs=1, seed=0, tokenizer=None,
                  served_model_name="chatts", limit_timeseries=15, block_size=None, num_gpu_blocks_override=None,
-                 enable_chunked_prefill=False, max_num_batched_tokens=512, kv_cache_dtype=None, max_logprobs=20):
+                 enable_chunked_prefill=False, max_num_batched_tokens=512, kv_cache_dtype=None, max_logprobs=20,
+                 speculative_config=None):
     """LLM (model + processor) -> Engine -> EngineThread -> FastAPI app.
     Tensor parallel (one process per GPU under torchrun, process group initialised): rank 0 gets the app, the other ranks get
     None after serving as followers until the leader shuts down (engine.follow)."""
@@ -366,7 +367,8 @@ def build_server(model, tensor_parallel_size=1, max_model_len=6000, max_num_seqs
     from .llm import LLM
     llm = LLM(model, tensor_parallel_size=tensor_parallel_size, max_model_len=max_model_len, max_num_seqs=max_num_seqs, seed=seed,
               tokenizer=tokenizer, limit_mm_per_prompt={"timeseries": limit_timeseries}, block_size=block_size,
-              num_gpu_blocks_override=num_gpu_blocks_override, kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs)
+              num_gpu_blocks_override=num_gpu_blocks_override, kv_cache_dtype=kv_cache_dtype, max_logprobs=max_logprobs,
+              speculative_config=speculative_config)
     control = ControlPlane.create() if tensor_parallel_size > 1 else None
     engine = Engine(llm.model, llm.processor, prefill_chunk_tokens=max_num_batched_tokens if enable_chunked_prefill else None)
     if control is not None and control.rank != 0:
@@ -399,7 +401,12 @@ def main():
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp16"], default="auto", help="auto: the float32 KV cache (parity grade); "
                     "fp16: half the cache bytes, logits ~2e-3 of the float32 oracle (speed mode)")
     ap.add_argument("--max-logprobs", type=int, default=20, help="largest logprobs / top_logprobs a request may ask for (0..64)")
+    ap.add_argument("--speculative-config", default=None, help="JSON like vLLM's: '{\"method\": \"ngram\", \"num_speculative_tokens\": 4, "
+                    "\"prompt_lookup_max\": 3, \"prompt_lookup_min\": 1}' - prompt-lookup speculative decoding for greedy requests "
+                    "(max-num-seqs 1, tensor-parallel-size 1)")
     args = ap.parse_args()
+    from .spec import parse_speculative_config
+    parse_speculative_config(args.speculative_config, args.tensor_parallel_size, args.max_num_seqs)      # fail before anything is loaded
     limit = int(dict(kv.split("=") for kv in args.limit_mm_per_prompt.split(",")).get("timeseries", 15))
     import uvicorn
     if args.tensor_parallel_size > 1:            # torchrun --nproc-per-node N -m chatts_amd.server --tensor-parallel-size N ...
@@ -416,7 +423,7 @@ def main():
                        served_model_name=args.served_model_name, limit_timeseries=limit, block_size=args.block_size,
                        num_gpu_blocks_override=args.num_gpu_blocks_override, enable_chunked_prefill=args.enable_chunked_prefill,
                        max_num_batched_tokens=args.max_num_batched_tokens, kv_cache_dtype=args.kv_cache_dtype,
-                       max_logprobs=args.max_logprobs)
+                       max_logprobs=args.max_logprobs, speculative_config=args.speculative_config)
     if app is None:
         return                                   # a follower rank: the leader has shut down
     try:

@@ -862,6 +862,67 @@ int chatts_decoder_decode_step(ChattsDecoder*, int32_t* pos_dev, int32_t* step_d
                                int64_t* token_dev, float* token_logit_dev, int64_t* out_tokens,
                                int n_splits, chatts_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Speculative decoding by prompt lookup (spec_decode.hip; vLLM's speculative_config {"method": "ngram"}, HF generate's
+ * prompt_lookup_num_tokens; NOT IN REFERENCE).  Greedy, one sequence, tp_world == 1.  One step proposes up to k draft tokens from the
+ * sequence's own token history, runs the last chosen token and the drafts (R = k + 1 rows) through all layers in one pass over the
+ * weights, takes the argmax of every row and keeps the longest prefix of drafts that equals the argmaxes, plus one more token: 1 .. R
+ * tokens per pass.  Purely additive to ABI 9: no existing struct or signature changes.
+ *
+ * hist [max_ctx] int32: hist[p] = the expanded token id at position p (<ts> patch positions hold their placeholder id); the caller
+ * fills positions 0 .. pos (the prompt and the first chosen token), chatts_spec_verify appends.
+ *
+ * chatts_spec_propose (one workgroup, deterministic): the context is hist[0 .. pos], pos = *pos_dev, hist[pos] = the last chosen token.
+ *   For a candidate end e < pos, m(e) = the largest m <= ngram_max with hist[e - j] == hist[pos - j] for all j < m.  The e with the
+ *   largest m(e) >= ngram_min wins, ties go to the smallest e.  draft[j] (j < k) = hist[e + 1 + j] if e + 1 + j <= pos, else -1; all
+ *   -1 when nothing matches.  spec_tokens [k + 1] int64 = hist[pos] followed by the drafts, an invalid draft (-1 or >= vocab) replaced
+ *   by id 0 (for the embedding lookup only).
+ * chatts_attention_verify: decode attention for `rows` (2 .. CHATTS_SPEC_MAX_ROWS) rows of ONE sequence at positions pos .. pos + rows - 1
+ *   (pos = *pos_dev): optional q / k RMSNorm, RoPE, the rows' K / V into the cache (the bits chatts_rope_kv_write stores); row i attends
+ *   cache rows [0, pos) and the in-flight rows 0 .. i, which are taken from qkv_raw through LDS, never read back from the cache.  One
+ *   workgroup per (kv head, 16-key tile slot) serves all rows x group-size query vectors; partials + combine as the decode form
+ *   (workspace >= chatts_attn_workspace(rows, n_q, n_splits)).  pos < 0 or pos + rows > max_ctx: nothing is written to the cache, out = 0.
+ * chatts_spec_verify (one wave): a = the number of leading i < k with a valid draft[i] == argmax[i]; e = min(a + 1, *out_capacity_dev -
+ *   step, max_ctx - (k + 1) - pos); e <= 0: nothing happens.  Otherwise argmax[0 .. e) goes to out_tokens[step ..] and hist[pos + 1 ..],
+ *   step += e, pos += e, *token_dev = argmax[e - 1], counters (int64 [4]) += (1, valid drafts, e - 1, e) = (steps, drafted, accepted,
+ *   emitted).  K / V rows of rejected drafts stay in the cache beyond pos and are overwritten by later steps; nothing reads past pos.
+ * ------------------------------------------------------------------------------------------- */
+#define CHATTS_SPEC_MAX_DRAFT 8
+#define CHATTS_SPEC_MAX_ROWS 9
+#define CHATTS_SPEC_MAX_NGRAM 8
+int chatts_spec_propose(const int32_t* pos_dev, const int32_t* hist, int max_ctx, int k, int ngram_min, int ngram_max, int64_t vocab,
+                        int32_t* draft, int64_t* spec_tokens, chatts_stream_t stream);
+int chatts_spec_verify(const int64_t* argmax, const int32_t* draft, int k, int64_t vocab, int32_t* pos_dev, int32_t* step_dev,
+                       int64_t* token_dev, int64_t* out_tokens, const int32_t* out_capacity_dev, int32_t* hist, int max_ctx,
+                       int64_t* counters, chatts_stream_t stream);
+int chatts_attention_verify(const float* qkv_raw, int rows, int n_q, int n_kv, const float* q_norm_w, const float* k_norm_w,
+                            float norm_eps, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
+                            const ChattsKvCache* cache, float* out, int n_splits, void* workspace, size_t workspace_bytes,
+                            chatts_stream_t stream);
+typedef struct ChattsSpecArgs {
+  int k;                        /* drafts per step, 1 .. CHATTS_SPEC_MAX_DRAFT */
+  int ngram_min, ngram_max;     /* 1 <= ngram_min <= ngram_max <= CHATTS_SPEC_MAX_NGRAM */
+  int n_splits;                 /* tile slots of the verify attention (lowered when the decoder's workspace holds fewer partials) */
+  int skip_propose;             /* != 0: draft / spec_tokens were filled by the caller (chatts_spec_propose on its own, or a test) */
+  int32_t* hist;                /* [max_ctx] */
+  int32_t* draft;               /* [k] */
+  int64_t* spec_tokens;         /* [k + 1] */
+  int64_t* argmax;              /* [k + 1] */
+  float* logits;                /* [k + 1, vocab_local] */
+  int32_t* pos_dev;
+  int32_t* step_dev;
+  int64_t* token_dev;
+  int64_t* out_tokens;
+  const int32_t* out_capacity_dev;
+  int64_t* counters;            /* [4] */
+} ChattsSpecArgs;
+/* One speculative step of the decoder's selected sequence (chatts_decoder_select_sequence), fully device-driven and graph-capturable:
+ * propose -> chatts_embed_token_batched(spec_tokens) into x rows 0 .. k -> every layer through the batched-row projections of
+ * chatts_decoder_layer_part_batched with chatts_attention_verify as the attention -> final norm + lm_head for k + 1 rows -> per-row
+ * argmax -> verify.  Refused with CHATTS_E_BADARG before anything is enqueued: null arguments, k / ngram sizes out of range,
+ * tp_world > 1, a sampler or logit controls set on the decoder. */
+int chatts_decoder_spec_step(ChattsDecoder*, const ChattsSpecArgs*, chatts_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
