@@ -212,12 +212,17 @@ int opt_get(ChattsOpt o, int dflt);      // the option's value, or dflt while it
 int device_cus();
 
 // Maximum of a row with torch.argmax's tie rule (first index), by a workgroup of 1024 threads; sv / si: 16-entry shared scratch.
-// The result is valid in thread 0 (argmax_kernel, and the greedy rows of sample_kernel's per-row mode).
+// The result is valid in thread 0 (argmax_kernel, and the greedy and degenerate rows of sample_kernel).
+// NaN entries never win a comparison, so they are skipped.  A row in which nothing exceeds -inf (all -inf, all NaN, or a mix of the
+// two) ends with best == -inf and an index that is either kArgmaxNone or whatever -inf entry of the scalar tail tied with the start
+// value: such a row selects index 0 - torch.argmax's answer for an all -inf row - and reports that entry's bits, so the token is
+// always inside the row.  The two-launch form (elementwise.hip) resolves the same case the same way.
+constexpr int64_t kArgmaxNone = 0x7fffffffffffffffLL;
 __device__ __forceinline__ void block_argmax_first(const float* __restrict__ logits, int64_t vocab, float* sv, int64_t* si, float& best,
                                                    int64_t& bi) {
   typedef float f32x4_t __attribute__((ext_vector_type(4)));
   best = -INFINITY;
-  bi = 0x7fffffffffffffffLL;
+  bi = kArgmaxNone;
   const int64_t v4 = ((reinterpret_cast<uintptr_t>(logits) & 15) == 0) ? vocab / 4 : 0;   // float4 body, scalar tail
   for (int64_t q = threadIdx.x; q < v4; q += 1024) {
     const f32x4_t v = reinterpret_cast<const f32x4_t*>(logits)[q];
@@ -242,6 +247,7 @@ __device__ __forceinline__ void block_argmax_first(const float* __restrict__ log
   if (threadIdx.x == 0) {
     for (int w = 1; w < 16; ++w)
       if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    if (!(best > -INFINITY)) { bi = 0; best = logits[0]; }
   }
 }
 

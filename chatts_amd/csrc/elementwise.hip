@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void argmax_part_kernel(const float* __restric
   const int64_t chunk = ((vocab + kArgmaxParts - 1) / kArgmaxParts + 3) / 4 * 4;
   const int64_t lo = blk * chunk, hi = lo + chunk < vocab ? lo + chunk : vocab;
   float best = -INFINITY;
-  int64_t bi = 0x7fffffffffffffffLL;
+  int64_t bi = kArgmaxNone;                            // a part past the end of the row keeps this: it loses every merge
   const bool vec = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
   const int64_t body_end = vec ? lo + (hi > lo ? (hi - lo) / 4 * 4 : 0) : lo;
   for (int64_t i = lo + threadIdx.x * 4; i < body_end; i += 1024) {
@@ -215,6 +215,7 @@ __global__ __launch_bounds__(256) void argmax_part_kernel(const float* __restric
 }
 
 __global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restrict__ part_v, const int64_t* __restrict__ part_i,
+                                                         const float* __restrict__ logits_all, int64_t logits_stride,
                                                          int64_t vocab_offset, int64_t* __restrict__ token_all,
                                                          float* __restrict__ token_logit_all, int64_t* __restrict__ out_tokens_all,
                                                          int64_t out_stride, int32_t* __restrict__ step_all,
@@ -234,6 +235,7 @@ __global__ __launch_bounds__(64) void argmax_final_kernel(const float* __restric
     int64_t* out_tokens = out_tokens_all ? out_tokens_all + (size_t)seq * out_stride : nullptr;
     int32_t* step_dev = step_all ? step_all + seq : nullptr;
     int32_t* pos_dev = pos_all ? pos_all + seq : nullptr;
+    if (!(best > -INFINITY)) { bi = 0; best = logits_all[(size_t)seq * logits_stride]; }   // nothing above -inf: block_argmax_first's rule
     const int64_t tok = bi + vocab_offset;
     if (token) *token = tok;
     if (token_logit) *token_logit = best;
@@ -257,7 +259,7 @@ int argmax_batched_scratch(const float* logits, int batch, int64_t logits_stride
   float* part_v = reinterpret_cast<float*>(part_i + (size_t)batch * kArgmaxParts);
   hipLaunchKernelGGL(argmax_part_kernel, dim3(kArgmaxParts, batch), dim3(256), 0, s, logits, logits_stride, vocab, part_v, part_i);
   CHATTS_CHECK_LAUNCH("argmax_part");
-  hipLaunchKernelGGL(argmax_final_kernel, dim3(batch), dim3(64), 0, s, part_v, part_i, vocab_offset, token, token_logit, out_tokens,
+  hipLaunchKernelGGL(argmax_final_kernel, dim3(batch), dim3(64), 0, s, part_v, part_i, logits, logits_stride, vocab_offset, token, token_logit, out_tokens,
                      out_stride, step_dev, pos_dev, pos_limit);
   CHATTS_CHECK_LAUNCH("argmax_final");
   return CHATTS_OK;

@@ -10,6 +10,8 @@
 //   max -> [top-k: 3-pass radix select of the k-th largest logit by COUNT] -> Z = sum e_i, e_i = exp((l_i - max)/T)
 //       -> [top-p: 3-pass radix select of the cut e* by MASS: largest e* with mass{e_i >= e*} >= top_p * Z]
 //       -> draw: first token (ascending id) whose running mass exceeds u * Z_kept.
+// A -inf logit carries no mass.  A row that holds a NaN or a +inf, or has no finite entry, is not sampled: the max pass sees it and
+// the whole workgroup takes the greedy path (block_argmax_first), which always writes a token inside the row and every side effect.
 // Masses are accumulated as 64-bit fixed point (e_i * 2^40, e_i <= 1): integer sums are order-independent, so the kept
 // set and the drawn token do not depend on atomic ordering or reduction trees - same seed, same logits => same token.
 // Ties at either cut are all kept (a sort keeps an arbitrary subset of them).
@@ -94,44 +96,56 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleParams p) {
   float inv_temp = p.inv_temp, top_p = p.top_p;
   int top_k = p.top_k;
   uint32_t seed = p.seed, seq_salt = (uint32_t)seq;
+  bool greedy = false;                               // uniform over the workgroup: it depends on the row only
   if (p.temp_rows) {
     const float tr = p.temp_rows[seq];
-    if (!(tr > 0.f)) {                               // a greedy row among sampling ones: torch.argmax's token, same side effects
-      __shared__ float gsv[16];
-      __shared__ int64_t gsi[16];
-      float best;
-      int64_t bi;
-      block_argmax_first(logits, V, gsv, gsi, best, bi);
-      if (t == 0) {
-        const int64_t tok = bi + p.vocab_offset;
-        if (p.token) p.token[seq] = tok;
-        if (p.token_logit) p.token_logit[seq] = best;
-        if (p.out_tokens && p.step && (p.out_stride == 0 || step < p.out_stride)) p.out_tokens[(size_t)seq * p.out_stride + step] = tok;
-        if (p.step) p.step[seq] = step + 1;
-        if (p.pos && p.pos[seq] >= 0 && (p.pos_limit <= 0 || p.pos[seq] < p.pos_limit)) p.pos[seq] += 1;
-        if (p.n_kept) p.n_kept[seq] = 1;
-        if (p.kept_mass) p.kept_mass[seq] = 0.f;
-      }
-      return;
+    if (!(tr > 0.f)) {
+      greedy = true;                                 // a greedy row among sampling ones
+    } else {
+      inv_temp = 1.0f / tr;
+      top_p = p.topp_rows ? p.topp_rows[seq] : 1.0f;
+      if (!(top_p > 0.f) || top_p > 1.0f) top_p = 1.0f;
+      top_k = p.topk_rows ? p.topk_rows[seq] : 0;
+      seed = p.seed_rows ? p.seed_rows[seq] : 0u;
+      seq_salt = 0u;                                 // the row's own seed identifies the request: its tokens do not depend on the slot
     }
-    inv_temp = 1.0f / tr;
-    top_p = p.topp_rows ? p.topp_rows[seq] : 1.0f;
-    if (!(top_p > 0.f) || top_p > 1.0f) top_p = 1.0f;
-    top_k = p.topk_rows ? p.topk_rows[seq] : 0;
-    seed = p.seed_rows ? p.seed_rows[seq] : 0u;
-    seq_salt = 0u;                                   // the row's own seed identifies the request: its tokens do not depend on the slot
   }
 
-  // ---- max
+  // ---- max.  A NaN counts as +inf here, so that m tells a degenerate row apart: m = +inf - the row holds a NaN or a +inf;
+  // m = -inf - it has no finite entry.  exp((l - m) / T) has no meaning for such a row: it is selected greedily.
   float m = -INFINITY;
-  for (int64_t i = t; i < V; i += 1024) m = fmaxf(m, logits[i]);
-  m = wave_max(m);
-  if (lane == 0) fred[wave] = m;
-  __syncthreads();
-  m = fred[0];
+  if (!greedy) {
+    for (int64_t i = t; i < V; i += 1024) {
+      const float l = logits[i];
+      m = fmaxf(m, l == l ? l : INFINITY);
+    }
+    m = wave_max(m);
+    if (lane == 0) fred[wave] = m;
+    __syncthreads();
+    m = fred[0];
 #pragma unroll
-  for (int w = 1; w < 16; ++w) m = fmaxf(m, fred[w]);
-  __syncthreads();
+    for (int w = 1; w < 16; ++w) m = fmaxf(m, fred[w]);
+    __syncthreads();
+    greedy = !(fabsf(m) < INFINITY);                 // every thread read the same fred[]: still uniform
+  }
+  if (greedy) {                                      // block_argmax_first's token (torch.argmax's on a row without NaN), same side effects
+    __shared__ float gsv[16];
+    __shared__ int64_t gsi[16];
+    float best;
+    int64_t bi;
+    block_argmax_first(logits, V, gsv, gsi, best, bi);
+    if (t == 0) {
+      const int64_t tok = bi + p.vocab_offset;
+      if (p.token) p.token[seq] = tok;
+      if (p.token_logit) p.token_logit[seq] = best;
+      if (p.out_tokens && p.step && (p.out_stride == 0 || step < p.out_stride)) p.out_tokens[(size_t)seq * p.out_stride + step] = tok;
+      if (p.step) p.step[seq] = step + 1;
+      if (p.pos && p.pos[seq] >= 0 && (p.pos_limit <= 0 || p.pos[seq] < p.pos_limit)) p.pos[seq] += 1;
+      if (p.n_kept) p.n_kept[seq] = 1;
+      if (p.kept_mass) p.kept_mass[seq] = 0.f;
+    }
+    return;
+  }
 
   // ---- top-k: the k-th largest logit by count (key of the cut; everything >= it is kept)
   uint32_t k_cut = 0;                                   // order_key >= 0 keeps everything

@@ -423,7 +423,16 @@ int chatts_attention_decode_batched(const float* qkv_raw, int batch, int n_q, in
                                     void* workspace, size_t workspace_bytes, chatts_stream_t stream);
 /* logits [V] float32 -> *token (first index of the maximum, like torch.argmax); optionally also
  * appends the token to out_tokens[*step_dev] and increments *step_dev and *pos_dev (decode loop
- * state kept on the device so that a hipGraph of one decode step is replayable). */
+ * state kept on the device so that a hipGraph of one decode step is replayable).
+ * Greedy selection on any row (this call, chatts_argmax_batched, chatts_argmax_batched_ws in both forms, the temperature-0 rows of
+ * chatts_sample_batched's per-row mode); a row is logits[0 .. vocab), the padding up to logits_stride is never read:
+ *   1. a row without NaN gives exactly torch.argmax's token: -inf entries are allowed, a +inf entry wins (the first of several), an
+ *      all -inf row gives index 0; token_logit is that entry's bits;
+ *   2. NaN entries are skipped when the row has a non-NaN entry above -inf: the token is torch.argmax of the row with every NaN
+ *      replaced by -inf;
+ *   3. any other row (only NaN, or only NaN and -inf) still gives a token in [vocab_offset, vocab_offset + vocab), the same one in
+ *      every form and every run (index 0 today), with token_logit = logits[token];
+ *   4. the side effects - the out_tokens cell, step + 1, pos with its parking and saturation rules - happen for every row. */
 int chatts_argmax(const float* logits, int64_t vocab, int64_t vocab_offset, int64_t* token,
                   float* token_logit, int64_t* out_tokens, int32_t* step_dev, int32_t* pos_dev,
                   chatts_stream_t stream);
@@ -455,6 +464,12 @@ int chatts_embed_token_batched(const int64_t* token_dev, int batch, const chatts
  * so a captured decode step replays with fresh draws and the same seed reproduces the same tokens.
  * Same side effects as chatts_argmax_batched (token, logit, out_tokens[step], ++step, ++pos).
  * temperature == 0 is greedy decoding: call chatts_argmax.
+ * Rows (logits[0 .. vocab); the padding up to logits_stride is never read), in scalar and per-row mode:
+ *   5. a REGULAR row has no NaN, no +inf and at least one finite entry; it follows the rule above.  A -inf id carries no mass, is
+ *      never drawn and is not counted in n_kept;
+ *   6. a DEGENERATE row holds a NaN or a +inf, or has no finite entry.  It is selected greedily by rules 1-3 of chatts_argmax, with
+ *      all side effects, token_logit = logits[token], n_kept = 1, kept_mass = 0 - what a temperature-0 row reports;
+ *   7. a degenerate row changes nothing in the other rows of the launch.
  * ------------------------------------------------------------------------------------------- */
 typedef struct ChattsSamplingArgs {
   float temperature;   /* > 0 */

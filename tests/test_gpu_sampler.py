@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from chatts_amd import _lib
-from oracle import sampler as osamp
+from tests.selection_ref import check_draw as _check_draw
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -41,27 +41,6 @@ def _sample(lib, logits, temperature, top_k, top_p, seed, steps=None, vocab_offs
         if step0[i] < 8:
             assert out[i, step0[i]] == tok[i]
     return tok.cpu().numpy(), tl.cpu().numpy(), nk.cpu().numpy(), km.cpu().numpy()
-
-
-def _check_draw(logits_row, tok, temperature, top_k, top_p, seed, seq, step, n_kept, kept_mass, vocab_offset=0):
-    """The device's choice is valid under the oracle's float64 rule (cuts and CDF boundaries get a float32 margin)."""
-    p, mass = osamp.kept_set(logits_row, temperature, top_k, top_p)
-    kept = p > 0
-    t = int(tok) - vocab_offset
-    assert 0 <= t < len(p)
-    # kept set: identical unless some probability sits within rounding distance of a cut
-    pf, _ = osamp.kept_set(logits_row, temperature, 0, 1.0)
-    cut = pf[kept].min()
-    ambiguous = int((np.abs(pf - cut) <= 2e-5 * cut).sum())
-    e_rel = np.exp((logits_row.astype(np.float64) - logits_row.max()) / temperature)
-    ambiguous += int((np.abs(e_rel - osamp.MASS_FLOOR) <= 1e-4 * osamp.MASS_FLOOR).sum())     # float32 exp around the mass floor
-    assert abs(int(n_kept) - int(kept.sum())) <= ambiguous, (n_kept, kept.sum(), ambiguous)
-    assert abs(float(kept_mass) - mass) <= 1e-4 + ambiguous * cut
-    assert pf[t] >= cut * (1 - 2e-5), "a token outside the kept set was drawn"
-    u = osamp.uniform24(seed, seq, step) / float(1 << 24)
-    cum = np.cumsum(p) / p.sum()
-    lo = cum[t] - p[t] / p.sum()
-    assert lo - 1e-4 <= u <= cum[t] + 1e-4, (u, lo, cum[t])
 
 
 @pytest.mark.parametrize("temperature,top_k,top_p", [(1.0, 0, 1.0), (0.2, 0, 1.0), (0.5, 0, 0.95), (1.0, 50, 1.0), (0.7, 20, 0.9),
