@@ -3,7 +3,19 @@
 // whose decoder is vLLM's Qwen2Model (NOT IN REFERENCE); layer math per oracle/qwen_decoder.py.
 // Nothing here allocates device memory or synchronises: every call only enqueues kernels on the
 // caller's stream, so a whole decode step can be captured into one hipGraph and replayed per token.
+//
+// Map of the schedule (top to bottom):
+//   Pass                    the mode of one whole-pass entry point (chained / verify rows / in-launch exchange), scoped: idle on every exit
+//   Proj, proj()            one projection (qkv, o, gate_up, down, lm_head) in every weight format; linear_args() + Copies { BF16, W8, W8_W4 }
+//                           is the only place a ChattsLinearArgs is filled; fp8_proj() / layer_half_f16q's args() are that for the two modes
+//   a_planes, c_planes, norm_into, resid_dest, request_post_norm     the recurring operand bindings and the fused-norm hand-off (d->normed)
+//   Rows                    WHAT a layer half works on: SEQ, SLOTS, VERIFY, PACKED, LAST - the entry points differ in this and nothing else
+//   layer_half()            precision mode for these rows (layer_half_fp8, layer_half_f16q) or the default kernels: attn_half() with
+//                           attention_stage() - the one part that differs by kind of rows - and mlp_half()
+//   run_layers()            the layer loop with the tensor-parallel sum after each half (sum_bulk / sum_unless_fused / none)
+//   chatts_decoder_prefill, _prefill_last, _prefill_packed, _decode_step, _decode_step_batched, _spec_step     Pass + run_layers + tail
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -34,23 +46,23 @@ struct ChattsDecoder {
   std::vector<ChattsLayerWeights> layers;
   ChattsDecoderBuffers b;
   int cur_seq = 0;          // sequence (KV-cache slot) the single-sequence entry points operate on
-  bool chain = false;       // set by the entry points that run the layers back to back themselves (chatts_decoder_prefill,
-                            // decode_step_batched): only then may a projection write the NEXT projection's normed operand
-  bool x_in_xn = false;     // batched step: o_proj left the residual stream in b.xn (ping-pong, see layer_part_batched); down_proj brings it back
-  bool normed = false;      // planes 0 already hold RMSNorm(x) for the projection that comes next (written by the previous
-                            // projection's fused epilogue): norm_into only binds them
   bool sampling = false;    // token selection of the decode steps: greedy argmax, or the sampler with `sa`
   ChattsSamplingArgs sa{};
   bool controls = false;    // logit controls (penalties / min_p) ahead of every selection, with `lc` (chatts_decoder_set_logit_controls)
   ChattsLogitControlArgs lc{};
   ChattsTpComm* tp = nullptr;   // tensor-parallel exchange (borrowed); required by the whole-step entry points when tp_world > 1
   bool prefill_f16q = false; // opt-in parity-grade mode (chatts_decoder_set_prefill_f16q): prefill chunks of >= 96 rows on the f16 + e4m3 operand split
-  bool normed_q = false;    // the f16q planes A already hold RMSNorm(x) for the projection that comes next (layer_part_f16q only)
   bool prefill_fp8 = false; // SPEED MODE (chatts_decoder_set_prefill_fp8): prefill chunks of >= 16 rows multiply fp8 x fp8 (gemm_fp8.hip)
-  bool fuse_tp = false;     // set by chatts_decoder_decode_step: the M == 1 o_proj / down_proj GEMVs carry the exchange in their own launch
-  bool tp_fused = false;    // ... and whether the last layer part's projection did (otherwise the caller launches chatts_allreduce)
-  int spec_rows = 0;        // set by chatts_decoder_spec_step: the `batch` rows of layer_part_batched are consecutive positions of the
-                            // SELECTED sequence (verify attention on its cache), not one token of each of the cache slots 0 .. batch - 1
+  // The mode of the running whole-pass entry point: set by Pass, idle (false / 0) outside one - also for layer halves called directly.
+  bool chain = false;       // the layers run back to back inside one call: only then may a projection write the NEXT projection's normed operand
+  bool fuse_tp = false;     // the M == 1 o_proj / down_proj GEMVs carry the exchange in their own launch (decode step; the last row's MLP)
+  int spec_rows = 0;        // > 0: the rows of the batched halves are consecutive positions of the SELECTED sequence (verify attention on its
+                            // cache), not one token of each of the cache slots 0 .. batch - 1 (speculative step)
+  // Hand-off from one launch to the next: set by the producer, cleared by the consumer (and by Pass on every exit).
+  bool normed = false;      // planes 0 already hold RMSNorm(x) for the next projection (the previous one's fused epilogue): norm_into only binds them
+  bool normed_q = false;    // ... the same for the f16q planes A (layer_half_f16q only)
+  bool x_in_xn = false;     // batched step: o_proj left the residual stream in b.xn (ping-pong, see attn_half); down_proj brings it back
+  bool tp_fused = false;    // the last residual projection carried its exchange itself (otherwise the caller launches chatts_allreduce)
 };
 
 static int64_t embed_rows(const ChattsDecoder* d) { return d->cfg.embed_rows > 0 ? d->cfg.embed_rows : d->cfg.vocab_local; }
@@ -198,6 +210,68 @@ static ChattsKvCache layer_cache(const ChattsDecoder* d, int layer, int seq) {
   return c;
 }
 
+static int max_batch(const ChattsDecoder* d) { return d->b.max_batch > 0 ? d->b.max_batch : 1; }      // (0 or 1 = single sequence)
+
+// The mode a whole-pass entry point runs in, for exactly as long as it runs: every exit path, error exits included, leaves the decoder
+// idle (no chaining, no verify rows, no in-launch exchange, no hand-off pending), so that nothing leaks into the next call.
+struct Pass {
+  ChattsDecoder* d;
+  Pass(ChattsDecoder* d_, bool chain, int spec_rows = 0, bool fuse_tp = false) : d(d_) {
+    idle();
+    d->chain = chain; d->spec_rows = spec_rows; d->fuse_tp = fuse_tp;
+  }
+  ~Pass() { idle(); }
+  void idle() { d->chain = false; d->spec_rows = 0; d->fuse_tp = false; d->normed = false; d->normed_q = false; d->x_in_xn = false; }
+};
+
+// ---- one description of a projection ---------------------------------------------------------------------------------------------
+enum Which { QKV, O, GATE_UP, DOWN, LM_HEAD };
+struct Proj {      // one [n, k] matrix in every format the decoder holds it in (NULL = that copy does not exist)
+  const chatts_bf16* w; const chatts_bf16* w_tiled; const float* bias;
+  const uint8_t* w8; const float* w8_scale;                               // 8-bit copy + row scale (cfg.w8_format)
+  const uint8_t* w4; const float* w4_sz; int w4_group;                    // 4-bit codes + (scale, scale * zero) per group
+  const chatts_f16* w16; const uint8_t* q8; const uint8_t* q8e;           // f16q triple: f16 high part, e4m3 residual, e8m0 row exponent
+  int n, k;
+};
+static Proj proj(const ChattsDecoder* d, int layer, Which which) {
+  const ChattsDecoderConfig& c = d->cfg;
+  const int H = c.hidden, na = c.n_q * kHeadDim;
+  if (which == LM_HEAD)
+    return {d->w.lm_head, nullptr, nullptr, d->w.lm_head8, d->w.lm_head8_scale, nullptr, nullptr, 0, nullptr, nullptr, nullptr, (int)c.vocab_local, H};
+  const ChattsLayerWeights& lw = d->layers[layer];
+  switch (which) {
+    case QKV: return {lw.qkv, lw.qkv_t, lw.qkv_bias, lw.qkv8, lw.qkv8_scale, lw.qkv4, lw.qkv4_sz, lw.w4_group, lw.qkv16, lw.qkv_q8, lw.qkv_q8e,
+                      (c.n_q + 2 * c.n_kv) * kHeadDim, H};
+    case O: return {lw.o, lw.o_t, nullptr, lw.o8, lw.o8_scale, lw.o4, lw.o4_sz, lw.w4_group, lw.o16, lw.o_q8, lw.o_q8e, H, na};
+    case GATE_UP: return {lw.gate_up, lw.gate_up_t, nullptr, lw.gate_up8, lw.gate_up8_scale, lw.gate_up4, lw.gate_up4_sz, lw.w4_group, lw.gate_up16,
+                          lw.gate_up_q8, lw.gate_up_q8e, 2 * c.inter, H};
+    default: return {lw.down, lw.down_t, nullptr, lw.down8, lw.down8_scale, lw.down4, lw.down4_sz, lw.w4_group, lw.down16, lw.down_q8, lw.down_q8e,
+                     H, c.inter};
+  }
+}
+static int out_cols(const Proj& p, int epilogue) { return epilogue == CHATTS_EPI_SWIGLU ? p.n / 2 : p.n; }
+
+// Which copies of the matrix a call offers the kernels besides bf16 (row-major + tiled).  The M == 1 GEMV streams the smallest copy it
+// is given, the M <= 16 weight-streaming GEMM the 8-bit one; a prefill chunk is MFMA-bound and gets neither.
+enum Copies { BF16, W8, W8_W4 };
+static void attach_w8(const ChattsDecoder* d, const Proj& p, ChattsLinearArgs* la) {
+  la->w8 = p.w8; la->w8_scale = p.w8_scale; la->ldw8 = p.k; la->w8_format = d->cfg.w8_format;
+}
+static void attach_w4(const Proj& p, ChattsLinearArgs* la) { la->w4 = p.w4; la->w4_sz = p.w4_sz; la->ldw4 = p.k / 2; la->w4_group = p.w4_group; }
+
+// The one place a ChattsLinearArgs is filled from a projection: dense rows in (lda = K) and out (ldc = the output width).  The caller
+// binds A (a / planes / norm_in_launch), C and, for o_proj / down_proj, the residual destination.
+static ChattsLinearArgs linear_args(const ChattsDecoder* d, const Proj& p, int m, int epilogue, Copies copies) {
+  ChattsLinearArgs la{};
+  la.w = p.w; la.w_tiled = p.w_tiled; la.bias = p.bias; la.m = m; la.n = p.n; la.k = p.k;
+  la.lda = p.k; la.ldw = p.k; la.ldc = out_cols(p, epilogue); la.epilogue = epilogue;
+  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
+  if (copies != BF16) attach_w8(d, p, &la);
+  if (copies == W8_W4) attach_w4(p, &la);
+  return la;
+}
+
+// ---- the recurring bindings ------------------------------------------------------------------------------------------------------
 // Projections whose A operand is a pair of bf16 hi / lo planes: prefill chunks of >= 96 rows (LDS-DMA GEMM) and batched
 // decode with 2..16 sequences on bf16 weights (weight-streaming kernel).
 static bool planes_path(const ChattsDecoder* d, int m, int k, bool fp8 = false) {
@@ -206,10 +280,26 @@ static bool planes_path(const ChattsDecoder* d, int m, int k, bool fp8 = false) 
   return m >= 96 && !fp8;
 }
 
+// A is planes pair `pair` (0: projection input, 1: gate_up output).  KEEP_F32 leaves the float32 `a` bound next to the planes: the
+// GEMM dispatch then takes the prefill kernel from 96 rows only and the float32 operand below (the split attention output).
+enum KeepA { DROP_F32, KEEP_F32 };
+static void a_planes(const ChattsDecoder* d, int pair, ChattsLinearArgs* la, KeepA keep = DROP_F32) {
+  if (keep == DROP_F32) la->a = nullptr;
+  la->a_hi = pair ? d->b.planes2_hi : d->b.planes_hi; la->a_lo = pair ? d->b.planes2_lo : d->b.planes_lo; la->ld_planes = la->k;
+}
+// C is planes pair 1 (the SwiGLU output goes straight into down_proj's operand format)
+static void c_planes(const ChattsDecoder* d, ChattsLinearArgs* la) {
+  la->c = nullptr; la->c_hi = d->b.planes2_hi; la->c_lo = d->b.planes2_lo; la->ld_cplanes = la->ldc;
+}
+// decode (M == 1): RMSNorm fused in the GEMV prologue
+static void norm_in_launch(const ChattsDecoder* d, const float* x, const float* norm_w, ChattsLinearArgs* la) {
+  la->a = x; la->norm_w = norm_w; la->norm_eps = d->cfg.rms_eps;
+}
+
 // x -> RMSNorm -> la's input: planes written by the norm kernel itself (plane path) or float32 xn.
 static int norm_into(ChattsDecoder* d, const float* norm_w, ChattsLinearArgs* la, chatts_stream_t stream) {
   if (planes_path(d, la->m, la->k, la->w8 != nullptr)) {
-    la->a = nullptr; la->a_hi = d->b.planes_hi; la->a_lo = d->b.planes_lo; la->ld_planes = la->k;
+    a_planes(d, 0, la);
     if (d->normed) { d->normed = false; return CHATTS_OK; }
     return chatts_rmsnorm_planes(d->b.x, norm_w, d->b.planes_hi, d->b.planes_lo, la->k, la->m, la->k, d->cfg.rms_eps, stream);
   }
@@ -218,18 +308,42 @@ static int norm_into(ChattsDecoder* d, const float* norm_w, ChattsLinearArgs* la
   return chatts_rmsnorm(d->b.x, norm_w, d->b.xn, la->m, la->k, d->cfg.rms_eps, stream);
 }
 
+// Where a residual projection (o_proj / down_proj) puts its result, for all three argument types:
+//   tensor parallel, fuse_in_launch   x = resid + sum over the ranks, inside the GEMV launch (ChattsLinearArgs.tp_reduce; d->tp_fused)
+//   tensor parallel otherwise         delta = the partial product: the caller all-reduces it into x
+//   one rank                          x = resid_in + product (resid_in: where the residual stream is - x, or xn in the batched ping-pong)
+template <class Args>
+static void resid_dest(ChattsDecoder* d, Args* la, bool fuse_in_launch, const float* resid_in) {
+  const bool tp = d->cfg.tp_world > 1;
+  d->tp_fused = false;
+  if (tp && !fuse_in_launch) { la->c = d->b.delta; la->epilogue = CHATTS_EPI_NONE; return; }
+  la->c = d->b.x; la->resid = tp ? d->b.x : resid_in; la->epilogue = CHATTS_EPI_RESID;
+  if constexpr (std::is_same<Args, ChattsLinearArgs>::value) {
+    if (tp) { la->tp_reduce = d->tp; d->tp_fused = true; }
+  }
+}
+
 // The residual-updating projection (o_proj / down_proj, tp_world == 1) also produces the NEXT projection's operand:
 // RMSNorm(x) with `next_norm_w` as planes 0, when that projection will take the plane path for the same M.
 static bool gemm_post_norm_small_m() { return opt_get(OPT_POST_NORM_SMALL_M, 1) != 0; }
 static void request_post_norm(ChattsDecoder* d, ChattsLinearArgs* la, const float* next_norm_w, bool next_fp8) {
   if (!d->chain || d->cfg.tp_world > 1 || !next_norm_w || la->epilogue != CHATTS_EPI_RESID) return;
   // the fused epilogue runs one workgroup per row - fine for a prefill chunk; at batched-decode M it needs several workgroups per row,
-  // which re-read resid while others write c: only when the caller gave it a c that does not alias resid (layer_part_batched)
+  // which re-read resid while others write c: only when the caller gave it a c that does not alias resid (the batched ping-pong)
   if (la->m < 64 && !(la->m <= 16 && la->c != la->resid && gemm_post_norm_small_m())) return;
   if (!planes_path(d, la->m, la->n, next_fp8)) return;
   la->post_norm_w = next_norm_w; la->post_norm_eps = d->cfg.rms_eps;
   la->post_hi = d->b.planes_hi; la->post_lo = d->b.planes_lo; la->ld_post = la->n;
   d->normed = true;
+}
+
+// row t - 1 of x -> row 0 (what follows a last-row prefill reads row 0)
+static int last_row_to_row0(ChattsDecoder* d, int t, chatts_stream_t stream) {
+  if (t <= 1) return CHATTS_OK;
+  const size_t H = (size_t)d->cfg.hidden;
+  const hipError_t e = hipMemcpyAsync(d->b.x, d->b.x + (size_t)(t - 1) * H, H * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream));
+  CHATTS_REQUIRE(e == hipSuccess, CHATTS_E_LAUNCH, "prefill_last: row copy: %s", hipGetErrorString(e));
+  return CHATTS_OK;
 }
 
 extern "C" int chatts_decoder_set_sampling(ChattsDecoder* d, const ChattsSamplingArgs* sa) {
@@ -247,7 +361,7 @@ extern "C" int chatts_decoder_set_tp(ChattsDecoder* d, ChattsTpComm* comm) {
   if (comm) {
     CHATTS_REQUIRE(chatts_tp_world(comm) == d->cfg.tp_world, CHATTS_E_BADARG, "decoder_set_tp: comm of %d ranks, decoder built for %d",
                    chatts_tp_world(comm), d->cfg.tp_world);
-    const int mb = d->b.max_batch > 0 ? d->b.max_batch : 1;
+    const int mb = max_batch(d);
     CHATTS_REQUIRE(chatts_tp_max_elems(comm) >= (int64_t)mb * d->cfg.hidden, CHATTS_E_SHAPE,
                    "decoder_set_tp: exchange buffer holds %lld elements, a step needs %lld", (long long)chatts_tp_max_elems(comm),
                    (long long)mb * d->cfg.hidden);
@@ -266,6 +380,17 @@ extern "C" int chatts_decoder_set_logit_controls(ChattsDecoder* d, const ChattsL
   return CHATTS_OK;
 }
 
+// ---- token selection and logprobs ------------------------------------------------------------------------------------------------
+// What a rank must have before it may gather the full-vocabulary logits into buffers.logits_full.  Call it, and every other check of
+// the caller, AHEAD of chatts_allgather: a refusal on one rank must not leave the others waiting in the collective.
+static int require_full_logits_tp(const ChattsDecoder* d, int batch, int64_t logits_stride, const char* name, const char* who_needs) {
+  CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "%s: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", name, d->cfg.tp_world);
+  CHATTS_REQUIRE(batch <= max_batch(d), CHATTS_E_SHAPE, "%s: batch %d exceeds max_batch %d", name, batch, max_batch(d));
+  CHATTS_REQUIRE(d->b.logits_full, CHATTS_E_BADARG, "%s: %s buffers.logits_full", name, who_needs);
+  CHATTS_REQUIRE(logits_stride == d->cfg.vocab_local || batch == 1, CHATTS_E_SHAPE, "%s: logits rows must be contiguous", name);
+  return CHATTS_OK;
+}
+
 // Selection with the logit controls on: penalised logits into lc->out, the TP = 1 selection on them, the chosen tokens into the state.
 // Tensor parallel: every rank gathers the full-vocabulary logits and does the same work on the same bytes -> the same token.
 static int select_controlled(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride, int64_t* token, float* token_logit,
@@ -275,14 +400,10 @@ static int select_controlled(ChattsDecoder* d, const float* logits, int batch, i
   int64_t vocab = c.vocab_local, offset = c.vocab_offset;
   int rc;
   if (c.tp_world > 1) {
-    CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "decoder_select_tokens: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", c.tp_world);
-    const int mb = d->b.max_batch > 0 ? d->b.max_batch : 1;
-    CHATTS_REQUIRE(batch <= mb, CHATTS_E_SHAPE, "decoder_select_tokens: batch %d exceeds max_batch %d", batch, mb);
-    CHATTS_REQUIRE(d->b.logits_full, CHATTS_E_BADARG, "decoder_select_tokens: logit controls under tensor parallelism need buffers.logits_full");
-    CHATTS_REQUIRE(logits_stride == c.vocab_local || batch == 1, CHATTS_E_SHAPE, "decoder_select_tokens: logits rows must be contiguous");
+    if ((rc = require_full_logits_tp(d, batch, logits_stride, "decoder_select_tokens", "logit controls under tensor parallelism need")) != 0)
+      return rc;
     vocab = c.vocab_local * c.tp_world; offset = 0;
   }
-  // validate before the collective: a refusal on one rank must not leave the others waiting in it
   CHATTS_REQUIRE(lc->state && lc->out && lc->state_stride >= vocab && lc->out_stride >= vocab, CHATTS_E_BADARG,
                  "decoder_select_tokens: logit controls need state and out rows of >= %lld cells", (long long)vocab);
   CHATTS_REQUIRE(d->b.workspace && d->b.workspace_bytes >= chatts_logit_controls_workspace(batch), CHATTS_E_WORKSPACE,
@@ -335,19 +456,17 @@ extern "C" int chatts_decoder_select_tokens_controlled(ChattsDecoder* d, const f
                                           out_stride, step_dev, pos_dev, pos_limit, d->b.workspace, d->b.workspace_bytes,
                                           reinterpret_cast<hipStream_t>(stream));
   }
-  CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "decoder_select_tokens: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", c.tp_world);
-  const int mb = d->b.max_batch > 0 ? d->b.max_batch : 1;
-  CHATTS_REQUIRE(batch <= mb, CHATTS_E_SHAPE, "decoder_select_tokens: batch %d exceeds max_batch %d", batch, mb);
   int rc;
   if (!sa) {      // one (max logit, global id) pair per rank and sequence instead of the [V / W] logits
+    CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "decoder_select_tokens: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", c.tp_world);
+    CHATTS_REQUIRE(batch <= max_batch(d), CHATTS_E_SHAPE, "decoder_select_tokens: batch %d exceeds max_batch %d", batch, max_batch(d));
     if ((rc = chatts_argmax_batched(logits, batch, logits_stride, c.vocab_local, c.vocab_offset, d->b.tp_pair_token, d->b.tp_pair_logit,
                                     nullptr, 0, nullptr, nullptr, 0, stream)) != 0) return rc;
     return chatts_tp_argmax(d->tp, batch, d->b.tp_pair_logit, d->b.tp_pair_token, token, token_logit, out_tokens, out_stride, step_dev,
                             pos_dev, pos_limit, stream);
   }
   // sampling: every rank draws from the gathered full-vocabulary logits with the same counter-hash variate -> the same token
-  CHATTS_REQUIRE(d->b.logits_full, CHATTS_E_BADARG, "decoder_select_tokens: sampling under tensor parallelism needs buffers.logits_full");
-  CHATTS_REQUIRE(logits_stride == c.vocab_local || batch == 1, CHATTS_E_SHAPE, "decoder_select_tokens: logits rows must be contiguous");
+  if ((rc = require_full_logits_tp(d, batch, logits_stride, "decoder_select_tokens", "sampling under tensor parallelism needs")) != 0) return rc;
   if ((rc = chatts_allgather(d->tp, logits, d->b.logits_full, batch, c.vocab_local, stream)) != 0) return rc;
   const int64_t vfull = c.vocab_local * c.tp_world;
   return chatts_sample_batched(d->b.logits_full, batch, vfull, vfull, 0, sa, token, token_logit, out_tokens, out_stride, step_dev,
@@ -366,15 +485,10 @@ extern "C" int chatts_decoder_logprobs(ChattsDecoder* d, const float* logits, in
   if (c.tp_world <= 1)
     return chatts_logprobs_batched(logits, batch, logits_stride, c.vocab_local, c.vocab_offset, k, token, step_dev, out_stride, out_lp,
                                    out_rank, out_top_ids, out_top_lp, d->b.workspace, d->b.workspace_bytes, stream);
-  CHATTS_REQUIRE(d->tp, CHATTS_E_BADARG, "decoder_logprobs: tp_world = %d but no exchange attached (chatts_decoder_set_tp)", c.tp_world);
-  const int mb = d->b.max_batch > 0 ? d->b.max_batch : 1;
-  CHATTS_REQUIRE(batch <= mb, CHATTS_E_SHAPE, "decoder_logprobs: batch %d exceeds max_batch %d", batch, mb);
-  CHATTS_REQUIRE(d->b.logits_full, CHATTS_E_BADARG, "decoder_logprobs: logprobs under tensor parallelism need buffers.logits_full");
-  CHATTS_REQUIRE(logits_stride == c.vocab_local || batch == 1, CHATTS_E_SHAPE, "decoder_logprobs: logits rows must be contiguous");
-  // validate before the collective: a refusal on one rank must not leave the others waiting in it
+  int rc;
+  if ((rc = require_full_logits_tp(d, batch, logits_stride, "decoder_logprobs", "logprobs under tensor parallelism need")) != 0) return rc;
   CHATTS_REQUIRE(k >= 0 && k <= CHATTS_LOGPROBS_MAX_K && (k == 0 || (out_top_ids && out_top_lp)) && out_lp && out_rank, CHATTS_E_BADARG,
                  "decoder_logprobs: k = %d / outputs", k);
-  int rc;
   if ((rc = chatts_allgather(d->tp, logits, d->b.logits_full, batch, c.vocab_local, stream)) != 0) return rc;
   const int64_t vfull = c.vocab_local * c.tp_world;
   return chatts_logprobs_batched(d->b.logits_full, batch, vfull, vfull, 0, k, token, step_dev, out_stride, out_lp, out_rank, out_top_ids,
@@ -382,8 +496,7 @@ extern "C" int chatts_decoder_logprobs(ChattsDecoder* d, const float* logits, in
 }
 
 extern "C" int chatts_decoder_select_sequence(ChattsDecoder* d, int seq) {
-  CHATTS_REQUIRE(d && seq >= 0 && seq < (d->b.max_batch > 0 ? d->b.max_batch : 1), CHATTS_E_BADARG,
-                 "decoder_select_sequence: slot %d out of range", seq);
+  CHATTS_REQUIRE(d && seq >= 0 && seq < max_batch(d), CHATTS_E_BADARG, "decoder_select_sequence: slot %d out of range", seq);
   d->cur_seq = seq;
   return CHATTS_OK;
 }
@@ -428,6 +541,93 @@ extern "C" int chatts_decoder_set_prefill_f16q(ChattsDecoder* d, int on) {
   return CHATTS_OK;
 }
 
+// ---- the rows a layer half works on ----------------------------------------------------------------------------------------------
+struct Rows {
+  enum Kind {
+    SEQ,        // m rows of the selected sequence at positions pos0 .. (or *pos_dev ..): a prefill chunk, or the decode row (m == 1)
+    SLOTS,      // one row of each of the cache slots 0 .. m - 1, row b at position pos_dev[b]: a batched decode step
+    VERIFY,     // m consecutive positions pos_dev[0 .. m) of the selected sequence, attended together: a speculative step
+    PACKED,     // the rows of n_segs prompts back to back, each segment with its own cache slot and pos0: packed prefill
+    LAST        // m rows of the selected sequence whose K / V go to the cache, while only the last row goes on (layer_last_row)
+  } kind;
+  int m, pos0;                                          // rows; first position on the host (SEQ, LAST)
+  const int32_t* pos_dev; int n_splits;                 // position(s) on the device (SEQ at m == 1, SLOTS, VERIFY) and their attention splits
+  const ChattsPrefillSegment* segs; int n_segs;         // PACKED
+};
+
+// RoPE + cache write (unless the qkv GEMM's epilogue did both) and causal attention of t rows `q` against the cache of `slot`
+static int rope_attend(ChattsDecoder* d, int layer, int slot, float* q, float* out, int t, int pos0, const int32_t* pos0_dev, bool rope_done,
+                       int ks, bool out_planes, chatts_stream_t stream) {
+  const ChattsDecoderConfig& c = d->cfg;
+  const ChattsLayerWeights& lw = d->layers[layer];
+  ChattsKvCache kc = layer_cache(d, layer, slot);
+  int rc;
+  if (!rope_done && (rc = chatts_rope_kv_write(q, t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos0, pos0_dev,
+                                               &kc, stream)) != 0) return rc;
+  return attention_impl(q, t, c.n_q, c.n_kv, pos0, pos0_dev, &kc, out, out_planes ? d->b.planes_hi : nullptr, out_planes ? d->b.planes_lo : nullptr,
+                        ks, d->b.workspace, d->b.workspace_bytes, stream);
+}
+
+// The attention stage between the qkv projection and o_proj - the one part that truly differs by the kind of rows.  tuned: the default
+// kernels' choices for a chunk (key split, planes written by the attention kernel); the precision modes and packed rows run it plain:
+// ks = 1, float32 output.  *wrote_planes: the attention kernel (or its combine) left its output in planes 0, o_proj's operand format.
+static int attention_stage(ChattsDecoder* d, int layer, const Rows& R, bool tuned, bool rope_done, bool* wrote_planes, chatts_stream_t stream) {
+  const ChattsDecoderConfig& c = d->cfg;
+  const ChattsLayerWeights& lw = d->layers[layer];
+  const int m = R.m, na = c.n_q * kHeadDim, qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim;
+  ChattsKvCache kc = layer_cache(d, layer, R.kind == Rows::SLOTS ? 0 : d->cur_seq);      // (packed rows: one cache per segment)
+  int rc;
+  *wrote_planes = false;
+  switch (R.kind) {
+    case Rows::SEQ: {
+      if (m == 1 && tuned)      // decode: RoPE + cache write fused into the attention kernel
+        return chatts_attention_decode_fused(d->b.qkv, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, R.pos0, R.pos_dev,
+                                             &kc, d->b.attn, R.n_splits, d->b.workspace, d->b.workspace_bytes, stream);
+      // long chunks: split the keys over 2 workgroups per (query tile, head) - one sequence has too few waves otherwise
+      const int env_ks = opt_get(OPT_ATTN_KSPLIT, 0);
+      // (the bf16x3 kernel is fast enough per tile that the second key split + its combine launch no longer pay: 73.3 us
+      // against 74.0 + 12 at T = 798; the float32-MFMA kernel, CHATTS_ATTN_BF16X3=0, still wants the split)
+      const bool f32_attn = opt_get(OPT_ATTN_BF16X3, 1) == 0;
+      int ks = env_ks >= 1 && env_ks <= 4 ? env_ks : (m >= 256 && f32_attn ? 2 : 1);
+      if (!tuned || chatts_attn_workspace(m, c.n_q, ks) > d->b.workspace_bytes) ks = 1;
+      // ... and, on the plane path, let the attention kernel (or its combine) write o_proj's operand format itself
+      *wrote_planes = tuned && m >= 16 && planes_path(d, m, na) && opt_get(OPT_ATTN_ROWS, 0) == 0;
+      return rope_attend(d, layer, d->cur_seq, d->b.qkv, d->b.attn, m, R.pos0, R.pos_dev, rope_done, ks, *wrote_planes, stream);
+    }
+    case Rows::SLOTS:
+    case Rows::VERIFY: {
+      *wrote_planes = planes_path(d, m, na, lw.o8 != nullptr);      // the combine writes o_proj's operand format
+      uint16_t* hi = *wrote_planes ? d->b.planes_hi : nullptr;
+      uint16_t* lo = *wrote_planes ? d->b.planes_lo : nullptr;
+      if (R.kind == Rows::VERIFY)
+        return attention_verify_impl(d->b.qkv, m, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, R.pos_dev, &kc,
+                                     d->b.attn, hi, lo, R.n_splits, d->b.workspace, d->b.workspace_bytes, stream);
+      return attention_decode_batched_impl(d->b.qkv, m, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, 0, R.pos_dev, &kc,
+                                           seq_stride(d), d->b.attn, hi, lo, R.n_splits, d->b.workspace, d->b.workspace_bytes, stream);
+    }
+    case Rows::PACKED:      // segment by segment, each against its own cache slot and positions
+      for (int i = 0; i < R.n_segs; ++i) {
+        const ChattsPrefillSegment& sg = R.segs[i];
+        if ((rc = rope_attend(d, layer, sg.slot, d->b.qkv + (size_t)sg.row0 * qkv_n, d->b.attn + (size_t)sg.row0 * na, sg.t, sg.pos0, nullptr, false,
+                              1, false, stream)) != 0) return rc;
+      }
+      return CHATTS_OK;
+    case Rows::LAST: {
+      if ((rc = chatts_rope_kv_write(d->b.qkv, m, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, R.pos0, nullptr, &kc,
+                                     stream)) != 0) return rc;
+      // one query row against pos0 + t keys: spread the 64-key tiles over up to 16 workgroups per kv head (one workgroup walking 800
+      // keys alone took 137 us in the round-2 trace)
+      int ks = (R.pos0 + m + 63) / 64;
+      if (ks > 16) ks = 16;
+      if (ks < 1 || chatts_attn_workspace(1, c.n_q, ks) > d->b.workspace_bytes) ks = 1;
+      if ((rc = chatts_attention(d->b.qkv + (size_t)(m - 1) * qkv_n, 1, c.n_q, c.n_kv, R.pos0 + m - 1, nullptr, &kc, d->b.attn, ks, d->b.workspace,
+                                 d->b.workspace_bytes, stream)) != 0) return rc;
+      return last_row_to_row0(d, m, stream);      // ... and from here on the layer is one row: row 0 of x
+    }
+  }
+  return CHATTS_E_BADARG;
+}
+
 struct F16qBuf { chatts_f16* hi; uint8_t* lo8; uint8_t* sc; };
 static F16qBuf f16q_buf(const ChattsDecoder* d, int pair) {
   const ChattsDecoderConfig& c = d->cfg;
@@ -442,104 +642,199 @@ static F16qBuf f16q_buf(const ChattsDecoder* d, int pair) {
   return b;
 }
 
-static int layer_part_f16q(ChattsDecoder* d, int layer, int part, int t, int pos0, const int32_t* pos0_dev, chatts_stream_t stream) {
+// f16q mode, one sequence's chunk of >= kF16qMinRows rows (Rows::SEQ): both halves.  Every operand travels as f16q planes: pair 0 is
+// the input of qkv / o_proj / gate_up, pair 1 the SwiGLU output that down_proj reads.
+static int layer_half_f16q(ChattsDecoder* d, int layer, int part, const Rows& R, chatts_stream_t stream) {
   StageRange stage(part == 0 ? "chatts.layer.attn.f16q" : "chatts.layer.mlp.f16q");
   const ChattsDecoderConfig& c = d->cfg;
   const ChattsLayerWeights& lw = d->layers[layer];
-  const bool tp = c.tp_world > 1;
-  const int H = c.hidden, na = c.n_q * kHeadDim, qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim;
+  const int H = c.hidden, na = c.n_q * kHeadDim, t = R.m;
   const F16qBuf A = f16q_buf(d, 0), B = f16q_buf(d, 1);
   d->normed = false;
-  d->tp_fused = false;
   int rc;
-  auto base = [&](ChattsLinearF16qArgs& q, const F16qBuf& in, int k, const chatts_f16* w16, const uint8_t* w8, const uint8_t* w8e, int n) {
-    q = ChattsLinearF16qArgs{};
-    q.a_hi = in.hi; q.a_lo8 = in.lo8; q.a_scale = in.sc; q.ld_a = k; q.ld_scale = k / 128;
-    q.w16 = w16; q.w8 = w8; q.w8_exp = w8e; q.ldw = k; q.m = t; q.n = n; q.k = k;
+  bool attn_planes;      // (always false here: the attention stage runs plain)
+  auto args = [&](const Proj& p, const F16qBuf& in, int epilogue) {
+    ChattsLinearF16qArgs q{};
+    q.a_hi = in.hi; q.a_lo8 = in.lo8; q.a_scale = in.sc; q.ld_a = p.k; q.ld_scale = p.k / 128;
+    q.w16 = p.w16; q.w8 = p.q8; q.w8_exp = p.q8e; q.ldw = p.k; q.bias = p.bias; q.m = t; q.n = p.n; q.k = p.k;
+    q.ldc = out_cols(p, epilogue); q.epilogue = epilogue;
     q.workspace = d->b.workspace; q.workspace_bytes = d->b.workspace_bytes;
     q.planes_tiled = 1; q.w_tiled = 1;      // every plane set and both weight copies in the kernel's own 1 KB / 512 B block order
+    return q;
   };
-  // a residual projection also writes RMSNorm(x) for the projection after it - only inside the entry points that run the layers back to back
-  auto post = [&](ChattsLinearF16qArgs& q, const float* next_norm_w) {
-    if (!d->chain || tp || !next_norm_w) return;
+  // pair 0 = RMSNorm(x), unless the projection before this one already wrote it (d->normed_q)
+  auto norm_into_A = [&](const float* norm_w) {
+    const bool have = d->normed_q;
+    d->normed_q = false;
+    return have ? CHATTS_OK : chatts_rmsnorm_f16q(d->b.x, norm_w, A.hi, A.lo8, A.sc, H, H / 128, t, H, c.rms_eps, 1, stream);
+  };
+  // a residual projection: its destination, and RMSNorm(x) for the projection after it - only inside the entry points that run the
+  // layers back to back (d->chain) on one rank
+  auto resid_into_x = [&](ChattsLinearF16qArgs& q, const float* next_norm_w) {
+    resid_dest(d, &q, false, d->b.x);
+    if (!d->chain || c.tp_world > 1 || !next_norm_w) return;
     q.post_norm_w = next_norm_w; q.post_norm_eps = c.rms_eps;
     q.post_hi = A.hi; q.post_lo8 = A.lo8; q.post_scale = A.sc; q.ld_post = H; q.ld_pscale = H / 128;
     d->normed_q = true;
   };
   ChattsLinearF16qArgs q;
   if (part == 0) {
-    if (!d->normed_q && (rc = chatts_rmsnorm_f16q(d->b.x, lw.input_norm, A.hi, A.lo8, A.sc, H, H / 128, t, H, c.rms_eps, 1, stream)) != 0) return rc;
-    d->normed_q = false;
-    base(q, A, H, lw.qkv16, lw.qkv_q8, lw.qkv_q8e, qkv_n);
-    q.bias = lw.qkv_bias; q.c = d->b.qkv; q.ldc = qkv_n; q.epilogue = CHATTS_EPI_NONE;
+    if ((rc = norm_into_A(lw.input_norm)) != 0) return rc;
+    q = args(proj(d, layer, QKV), A, CHATTS_EPI_NONE);
+    q.c = d->b.qkv;
     if ((rc = chatts_linear_f16q(&q, stream)) != 0) return rc;
-    ChattsKvCache kc = layer_cache(d, layer, d->cur_seq);
-    if ((rc = chatts_rope_kv_write(d->b.qkv, t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos0, pos0_dev,
-                                   &kc, stream)) != 0) return rc;
-    if ((rc = attention_impl(d->b.qkv, t, c.n_q, c.n_kv, pos0, pos0_dev, &kc, d->b.attn, nullptr, nullptr, 1, d->b.workspace,
-                             d->b.workspace_bytes, stream)) != 0) return rc;
+    if ((rc = attention_stage(d, layer, R, false, false, &attn_planes, stream)) != 0) return rc;
     if ((rc = chatts_split_f16q(d->b.attn, t, na, na, A.hi, A.lo8, A.sc, na, na / 128, 1, stream)) != 0) return rc;
-    base(q, A, na, lw.o16, lw.o_q8, lw.o_q8e, H);
-    q.ldc = H;
-    if (tp) { q.c = d->b.delta; q.epilogue = CHATTS_EPI_NONE; }
-    else { q.c = d->b.x; q.resid = d->b.x; q.epilogue = CHATTS_EPI_RESID; post(q, lw.post_norm); }
+    q = args(proj(d, layer, O), A, CHATTS_EPI_NONE);
+    resid_into_x(q, lw.post_norm);
     return chatts_linear_f16q(&q, stream);
   }
-  if (!d->normed_q && (rc = chatts_rmsnorm_f16q(d->b.x, lw.post_norm, A.hi, A.lo8, A.sc, H, H / 128, t, H, c.rms_eps, 1, stream)) != 0) return rc;
-  d->normed_q = false;
-  base(q, A, H, lw.gate_up16, lw.gate_up_q8, lw.gate_up_q8e, 2 * c.inter);
-  q.epilogue = CHATTS_EPI_SWIGLU; q.ldc = c.inter;
+  if ((rc = norm_into_A(lw.post_norm)) != 0) return rc;
+  q = args(proj(d, layer, GATE_UP), A, CHATTS_EPI_SWIGLU);
   q.c_hi = B.hi; q.c_lo8 = B.lo8; q.c_scale = B.sc; q.ld_cplanes = c.inter; q.ld_cscale = c.inter / 128;
   if ((rc = chatts_linear_f16q(&q, stream)) != 0) return rc;
-  base(q, B, c.inter, lw.down16, lw.down_q8, lw.down_q8e, H);
-  q.ldc = H;
-  if (tp) { q.c = d->b.delta; q.epilogue = CHATTS_EPI_NONE; }
-  else { q.c = d->b.x; q.resid = d->b.x; q.epilogue = CHATTS_EPI_RESID; post(q, layer + 1 < c.n_layers ? d->layers[layer + 1].input_norm : nullptr); }
+  q = args(proj(d, layer, DOWN), B, CHATTS_EPI_NONE);
+  resid_into_x(q, layer + 1 < c.n_layers ? d->layers[layer + 1].input_norm : nullptr);
   return chatts_linear_f16q(&q, stream);
 }
 
-static int layer_part_fp8(ChattsDecoder* d, int layer, int part, int t, int pos0, const int32_t* pos0_dev, chatts_stream_t stream) {
+// Speed mode, one projection: rows of `src` quantised per token (after RMSNorm with norm_w, when given) into scratch set `set`, then the
+// fp8 x fp8 GEMM on them into c - or, c == NULL, to the residual destination.  Scratch sets (bytes | row scales): 0 = planes_hi | xn
+// (qkv, gate_up), 1 = planes_lo | xn + t_max (o_proj), 2 = planes2_hi | xn + t_max (down_proj).
+static int fp8_proj(ChattsDecoder* d, const Proj& p, int t, const float* src, const float* norm_w, int set, int epilogue, float* c,
+                    chatts_stream_t stream) {
+  uint8_t* a8 = reinterpret_cast<uint8_t*>(set == 0 ? d->b.planes_hi : set == 1 ? d->b.planes_lo : d->b.planes2_hi);
+  float* scale = set == 0 ? d->b.xn : d->b.xn + d->b.t_max;
+  const int rc = chatts_quantize_rows_fp8(src, t, p.k, p.k, norm_w, norm_w ? d->cfg.rms_eps : 0.f, a8, p.k, scale, stream);
+  if (rc) return rc;
+  ChattsLinearFp8Args f{};
+  f.a8 = a8; f.a_scale = scale; f.w8 = p.w8; f.w_scale = p.w8_scale; f.bias = p.bias; f.c = c;
+  f.m = t; f.n = p.n; f.k = p.k; f.lda8 = p.k; f.ldw8 = p.k; f.ldc = out_cols(p, epilogue); f.epilogue = epilogue;
+  if (!c) resid_dest(d, &f, false, d->b.x);
+  return chatts_linear_fp8(&f, stream);
+}
+
+// speed mode, chunks of >= 16 rows of one sequence (Rows::SEQ) or of packed prompts (Rows::PACKED, attention half): both halves
+static int layer_half_fp8(ChattsDecoder* d, int layer, int part, const Rows& R, chatts_stream_t stream) {
+  const ChattsLayerWeights& lw = d->layers[layer];
+  const int t = R.m;
+  d->normed = false; d->normed_q = false;
+  int rc;
+  bool attn_planes;      // (always false here: the attention stage runs plain)
+  if (part == 0) {
+    if ((rc = fp8_proj(d, proj(d, layer, QKV), t, d->b.x, lw.input_norm, 0, CHATTS_EPI_NONE, d->b.qkv, stream)) != 0) return rc;
+    if ((rc = attention_stage(d, layer, R, false, false, &attn_planes, stream)) != 0) return rc;
+    return fp8_proj(d, proj(d, layer, O), t, d->b.attn, nullptr, 1, CHATTS_EPI_NONE, nullptr, stream);
+  }
+  if ((rc = fp8_proj(d, proj(d, layer, GATE_UP), t, d->b.x, lw.post_norm, 0, CHATTS_EPI_SWIGLU, d->b.act, stream)) != 0) return rc;
+  return fp8_proj(d, proj(d, layer, DOWN), t, d->b.act, nullptr, 2, CHATTS_EPI_NONE, nullptr, stream);
+}
+
+// ---- the default kernels: attention half and MLP half, once each -----------------------------------------------------------------
+// RMSNorm -> qkv (+ bias) -> RoPE / cache write / attention -> o_proj (+ residual, or the partial sum for the TP all-reduce)
+static int attn_half(ChattsDecoder* d, int layer, const Rows& R, chatts_stream_t stream) {
   const ChattsDecoderConfig& c = d->cfg;
   const ChattsLayerWeights& lw = d->layers[layer];
+  const int H = c.hidden, na = c.n_q * kHeadDim, m = R.m;
   const bool tp = c.tp_world > 1;
-  const int H = c.hidden, na = c.n_q * kHeadDim, qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim;
-  uint8_t* a8 = reinterpret_cast<uint8_t*>(d->b.planes_hi);
-  uint8_t* b8 = reinterpret_cast<uint8_t*>(d->b.planes_lo);
-  float* sa = d->b.xn;
-  float* sb = d->b.xn + d->b.t_max;
-  d->normed = false;
-  d->tp_fused = false;
+  // What differs by entry point, besides the attention stage:
+  const bool seq = R.kind == Rows::SEQ, last = R.kind == Rows::LAST;
+  const bool gemv = seq && m == 1;              // decode_step (layer_part at t == 1): norm fused in the GEMV prologue, 8- and 4-bit copies
+  const bool slots = R.kind == Rows::SLOTS || R.kind == Rows::VERIFY;      // decode_step_batched / spec_step: 8-bit copies, ping-pong
+  const Copies qkv_copies = gemv ? W8_W4 : slots ? W8 : BF16;               // (prefill, prefill_last, prefill_packed: bf16 only)
+  const Copies o_copies = gemv || last ? W8_W4 : slots ? W8 : BF16;         // (the last row's o_proj is a GEMV like the decode step's)
+  const bool rope_in_gemm = seq && m > 1 && opt_get(OPT_ROPE_FUSE, 1) != 0;    // prefill / prefill_last: the qkv GEMM's split-K epilogue (when
+                                                                            // it has one) also rotates q / k and fills the cache
+  const bool split_attn = seq || R.kind == Rows::PACKED;                    // float32 attention output on the plane path: split it for o_proj
+  const bool next_fp8 = slots && lw.gate_up8 != nullptr;                    // planes_path flag of the projection after o_proj (prefill: false)
   int rc;
-  ChattsLinearFp8Args f{};
-  if (part == 0) {
-    if ((rc = chatts_quantize_rows_fp8(d->b.x, t, H, H, lw.input_norm, c.rms_eps, a8, H, sa, stream)) != 0) return rc;
-    f.a8 = a8; f.a_scale = sa; f.w8 = lw.qkv8; f.w_scale = lw.qkv8_scale; f.bias = lw.qkv_bias; f.c = d->b.qkv;
-    f.m = t; f.n = qkv_n; f.k = H; f.lda8 = H; f.ldw8 = H; f.ldc = qkv_n; f.epilogue = CHATTS_EPI_NONE;
-    if ((rc = chatts_linear_fp8(&f, stream)) != 0) return rc;
+  ChattsLinearArgs la = linear_args(d, proj(d, layer, QKV), m, CHATTS_EPI_NONE, qkv_copies);
+  la.c = d->b.qkv;
+  if (gemv) norm_in_launch(d, d->b.x, lw.input_norm, &la);
+  else if ((rc = norm_into(d, lw.input_norm, &la, stream)) != 0) return rc;
+  bool rope_done = false;
+  if (rope_in_gemm) {
     ChattsKvCache kc = layer_cache(d, layer, d->cur_seq);
-    if ((rc = chatts_rope_kv_write(d->b.qkv, t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos0, pos0_dev,
-                                   &kc, stream)) != 0) return rc;
-    if ((rc = attention_impl(d->b.qkv, t, c.n_q, c.n_kv, pos0, pos0_dev, &kc, d->b.attn, nullptr, nullptr, 1, d->b.workspace,
-                             d->b.workspace_bytes, stream)) != 0) return rc;
-    if ((rc = chatts_quantize_rows_fp8(d->b.attn, t, na, na, nullptr, 0.f, b8, na, sb, stream)) != 0) return rc;
-    f = ChattsLinearFp8Args{};
-    f.a8 = b8; f.a_scale = sb; f.w8 = lw.o8; f.w_scale = lw.o8_scale; f.m = t; f.n = H; f.k = na; f.lda8 = na; f.ldw8 = na; f.ldc = H;
-    if (tp) { f.c = d->b.delta; f.epilogue = CHATTS_EPI_NONE; }
-    else { f.c = d->b.x; f.resid = d->b.x; f.epilogue = CHATTS_EPI_RESID; }
-    return chatts_linear_fp8(&f, stream);
+    RopeFuse rf;
+    if ((rc = rope_fuse_prepare(m, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, R.pos0, R.pos_dev, &kc, &rf)) != 0)
+      return rc;
+    if ((rc = linear_impl(&la, stream, &rf, &rope_done)) != 0) return rc;
+  } else if ((rc = chatts_linear(&la, stream)) != 0) {
+    return rc;
   }
-  if ((rc = chatts_quantize_rows_fp8(d->b.x, t, H, H, lw.post_norm, c.rms_eps, a8, H, sa, stream)) != 0) return rc;
-  f.a8 = a8; f.a_scale = sa; f.w8 = lw.gate_up8; f.w_scale = lw.gate_up8_scale; f.c = d->b.act;
-  f.m = t; f.n = 2 * c.inter; f.k = H; f.lda8 = H; f.ldw8 = H; f.ldc = c.inter; f.epilogue = CHATTS_EPI_SWIGLU;
-  if ((rc = chatts_linear_fp8(&f, stream)) != 0) return rc;
-  uint8_t* c8 = reinterpret_cast<uint8_t*>(d->b.planes2_hi);
-  if ((rc = chatts_quantize_rows_fp8(d->b.act, t, c.inter, c.inter, nullptr, 0.f, c8, c.inter, sb, stream)) != 0) return rc;
-  f = ChattsLinearFp8Args{};
-  f.a8 = c8; f.a_scale = sb; f.w8 = lw.down8; f.w_scale = lw.down8_scale; f.m = t; f.n = H; f.k = c.inter; f.lda8 = c.inter; f.ldw8 = c.inter;
-  f.ldc = H;
-  if (tp) { f.c = d->b.delta; f.epilogue = CHATTS_EPI_NONE; }
-  else { f.c = d->b.x; f.resid = d->b.x; f.epilogue = CHATTS_EPI_RESID; }
-  return chatts_linear_fp8(&f, stream);
+  bool attn_planes = false;
+  if ((rc = attention_stage(d, layer, R, true, rope_done, &attn_planes, stream)) != 0) return rc;
+
+  la = linear_args(d, proj(d, layer, O), last ? 1 : m, CHATTS_EPI_NONE, o_copies);
+  la.a = d->b.attn;
+  if (attn_planes) {
+    a_planes(d, 0, &la);
+  } else if (split_attn && planes_path(d, m, na)) {      // the VALU attention kernel writes float32: split it
+    if ((rc = chatts_split_bf16x2(d->b.attn, m, na, na, d->b.planes_hi, d->b.planes_lo, na, stream)) != 0) return rc;
+    a_planes(d, 0, &la, KEEP_F32);
+  }
+  // x += sum over the ranks inside the GEMV launch: the decode step when it asked for it (d->fuse_tp), the last row always
+  resid_dest(d, &la, ((gemv && d->fuse_tp && d->tp) || last) && !la.w4, d->b.x);
+  if (slots) {
+    // The residual stream ping-pongs x -> xn (here) -> x (down_proj) inside a chained step, so that the post-norm epilogue may use
+    // several workgroups per row (they read resid columns other workgroups update: c must not alias resid).
+    d->x_in_xn = !tp && d->chain && d->b.xn && m <= 16 && planes_path(d, m, H, next_fp8);
+    if (d->x_in_xn) la.c = d->b.xn;
+  }
+  if (!last) request_post_norm(d, &la, lw.post_norm, next_fp8);
+  if (slots && d->x_in_xn && !la.post_norm_w) { la.c = d->b.x; d->x_in_xn = false; }      // not fused after all: the norm launch reads x
+  rc = chatts_linear(&la, stream);
+  if (last && rc == CHATTS_OK && tp && !d->tp_fused) rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, H, stream);
+  return rc;
+}
+
+// RMSNorm -> gate_up + SwiGLU -> down (+ residual / partial).  Rows::SEQ (packed prefill and the last row run it as such) or SLOTS / VERIFY.
+static int mlp_half(ChattsDecoder* d, int layer, const Rows& R, chatts_stream_t stream) {
+  const ChattsDecoderConfig& c = d->cfg;
+  const ChattsLayerWeights& lw = d->layers[layer];
+  const int H = c.hidden, m = R.m;
+  const bool last_layer = layer + 1 >= c.n_layers;
+  // What differs by entry point:
+  const bool gemv = R.kind == Rows::SEQ && m == 1;      // decode_step, and row 0 of layer_last_row: fused norm, 8- and 4-bit copies
+  const bool slots = R.kind == Rows::SLOTS || R.kind == Rows::VERIFY;      // decode_step_batched / spec_step: 8-bit copies
+  const Copies copies = gemv ? W8_W4 : slots ? W8 : BF16;                   // (prefill chunks: bf16 only)
+  // SwiGLU output straight into down_proj's operand planes.  Prefill asks for down_proj's K alone; the batched step asks with each
+  // projection's own 8-bit flag and wants gate_up on the plane path too.
+  const bool act_planes = slots ? planes_path(d, m, c.inter, lw.down8 != nullptr) && planes_path(d, m, H, lw.gate_up8 != nullptr)
+                                : m > 1 && planes_path(d, m, c.inter);
+  const float* resid_in = slots && d->x_in_xn ? d->b.xn : d->b.x;           // batched ping-pong: o_proj left the residual stream in xn
+  // what down_proj pre-norms for: the next layer's qkv; after the last layer final_norm + lm_head in the batched step
+  // (chatts_decoder_logits_batched follows) and nothing for one sequence (chatts_decoder_logits norms its one row in the GEMV)
+  const float* next_norm_w = !last_layer ? d->layers[layer + 1].input_norm : slots ? d->w.final_norm : nullptr;
+  const bool next_fp8 = slots && (!last_layer ? d->layers[layer + 1].qkv8 : d->w.lm_head8) != nullptr;
+  int rc;
+  ChattsLinearArgs la = linear_args(d, proj(d, layer, GATE_UP), m, CHATTS_EPI_SWIGLU, copies);
+  la.c = d->b.act;
+  if (gemv) norm_in_launch(d, d->b.x, lw.post_norm, &la);
+  else if ((rc = norm_into(d, lw.post_norm, &la, stream)) != 0) return rc;
+  if (act_planes) c_planes(d, &la);
+  if ((rc = chatts_linear(&la, stream)) != 0) return rc;
+
+  la = linear_args(d, proj(d, layer, DOWN), m, CHATTS_EPI_NONE, copies);
+  la.a = d->b.act;
+  if (act_planes) a_planes(d, 1, &la);
+  resid_dest(d, &la, gemv && d->fuse_tp && d->tp && !la.w4, resid_in);
+  if (slots) d->x_in_xn = false;
+  request_post_norm(d, &la, next_norm_w, next_fp8);
+  return chatts_linear(&la, stream);
+}
+
+constexpr int kFp8MinRows = 16;       // speed mode: chunks below this take the default kernels
+
+// One layer half on rows R: the precision mode that applies to these rows, or the default kernels.
+static int layer_half(ChattsDecoder* d, int layer, int part, const Rows& R, chatts_stream_t stream) {
+  const bool chunk = R.kind == Rows::SEQ || R.kind == Rows::PACKED;      // the opt-in modes are for prefill chunks only
+  if (chunk && d->prefill_fp8 && R.m >= kFp8MinRows) return layer_half_fp8(d, layer, part, R, stream);
+  if (R.kind == Rows::SEQ && d->prefill_f16q && R.m >= kF16qMinRows) return layer_half_f16q(d, layer, part, R, stream);
+  d->normed_q = false;        // (a following f16q half recomputes its norm: planes 0 are about to hold bf16 data)
+  if (part == 0 && (R.kind == Rows::PACKED || R.kind == Rows::LAST)) return attn_half(d, layer, R, stream);      // (no stage range of their own)
+  StageRange stage(part == 0 ? "chatts.layer.attn" : "chatts.layer.mlp");
+  return part == 0 ? attn_half(d, layer, R, stream) : mlp_half(d, layer, R, stream);
 }
 
 extern "C" int chatts_decoder_layer_part(ChattsDecoder* d, int layer, int part, int t, int pos0,
@@ -547,120 +842,7 @@ extern "C" int chatts_decoder_layer_part(ChattsDecoder* d, int layer, int part, 
   CHATTS_REQUIRE(d && layer >= 0 && layer < d->cfg.n_layers && (part == 0 || part == 1), CHATTS_E_BADARG,
                  "decoder_layer_part: bad arguments");
   CHATTS_REQUIRE(t >= 1 && t <= d->b.t_max, CHATTS_E_SHAPE, "decoder_layer_part: t=%d exceeds buffers (%d)", t, d->b.t_max);
-  if (d->prefill_fp8 && t >= 16) return layer_part_fp8(d, layer, part, t, pos0, pos0_dev, stream);      // speed mode, prefill chunks only
-  if (d->prefill_f16q && t >= kF16qMinRows) return layer_part_f16q(d, layer, part, t, pos0, pos0_dev, stream);
-  d->normed_q = false;        // (a following f16q half recomputes its norm: planes 0 are about to hold bf16 data)
-  StageRange stage(part == 0 ? "chatts.layer.attn" : "chatts.layer.mlp");
-  const ChattsDecoderConfig& c = d->cfg;
-  const ChattsLayerWeights& lw = d->layers[layer];
-  const bool tp = c.tp_world > 1;
-  const int H = c.hidden;
-  int rc;
-  ChattsLinearArgs la;
-  if (part == 0) {
-    const int qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim;
-    // RMSNorm -> QKV (+bias).  Decode: norm fused in the GEMV prologue; prefill: separate kernel.
-    la = ChattsLinearArgs{};
-    la.w = lw.qkv; la.w_tiled = lw.qkv_t; la.bias = lw.qkv_bias; la.c = d->b.qkv; la.m = t; la.n = qkv_n; la.k = H;
-    la.lda = H; la.ldw = H; la.ldc = qkv_n; la.epilogue = CHATTS_EPI_NONE;
-    la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-    if (t == 1) {
-      la.a = d->b.x; la.norm_w = lw.input_norm; la.norm_eps = c.rms_eps;
-      la.w8 = lw.qkv8; la.w8_scale = lw.qkv8_scale; la.ldw8 = H; la.w8_format = d->cfg.w8_format;
-      la.w4 = lw.qkv4; la.w4_sz = lw.qkv4_sz; la.ldw4 = H / 2; la.w4_group = lw.w4_group;
-    } else {
-      if ((rc = norm_into(d, lw.input_norm, &la, stream)) != 0) return rc;
-    }
-    ChattsKvCache kc = layer_cache(d, layer, d->cur_seq);
-    bool rope_done = false;
-    const bool rope_fuse = opt_get(OPT_ROPE_FUSE, 1) != 0;
-    if (t > 1 && rope_fuse) {   // prefill: the projection's split-K epilogue (when it has one) also rotates q / k and fills the cache
-      RopeFuse rf;
-      if ((rc = rope_fuse_prepare(t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos0, pos0_dev, &kc,
-                                  &rf)) != 0) return rc;
-      if ((rc = linear_impl(&la, stream, &rf, &rope_done)) != 0) return rc;
-    } else if ((rc = chatts_linear(&la, stream)) != 0) {
-      return rc;
-    }
-    bool attn_out_planes = false;
-    if (t == 1) {   // decode: RoPE + cache write fused into the attention kernel
-      if ((rc = chatts_attention_decode_fused(d->b.qkv, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab,
-                                                     d->w.sin_tab, pos0, pos0_dev, &kc, d->b.attn, n_splits, d->b.workspace,
-                                                     d->b.workspace_bytes, stream)) != 0) {
-        return rc;
-      }
-    } else {
-      if (!rope_done && (rc = chatts_rope_kv_write(d->b.qkv, t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab,
-                                                   d->w.sin_tab, pos0, pos0_dev, &kc, stream)) != 0) return rc;
-      // long chunks: split the keys over 2 workgroups per (query tile, head) - one sequence has too few waves otherwise
-      const int env_ks = opt_get(OPT_ATTN_KSPLIT, 0);
-      // (the bf16x3 kernel is fast enough per tile that the second key split + its combine launch no longer pay: 73.3 us
-      // against 74.0 + 12 at T = 798; the float32-MFMA kernel, CHATTS_ATTN_BF16X3=0, still wants the split)
-      const bool f32_attn = opt_get(OPT_ATTN_BF16X3, 1) == 0;
-      int ks = env_ks >= 1 && env_ks <= 4 ? env_ks : (t >= 256 && f32_attn ? 2 : 1);
-      if (chatts_attn_workspace(t, c.n_q, ks) > d->b.workspace_bytes) ks = 1;
-      // ... and, on the plane path, let the attention kernel (or its combine) write o_proj's operand format itself
-      const bool out_planes = t >= 16 && planes_path(d, t, c.n_q * kHeadDim) && opt_get(OPT_ATTN_ROWS, 0) == 0;
-      if ((rc = attention_impl(d->b.qkv, t, c.n_q, c.n_kv, pos0, pos0_dev, &kc, d->b.attn, out_planes ? d->b.planes_hi : nullptr,
-                               out_planes ? d->b.planes_lo : nullptr, ks, d->b.workspace, d->b.workspace_bytes, stream)) != 0)
-        return rc;
-      attn_out_planes = out_planes;
-    }
-    // o_proj (+ residual, or partial sum for the TP all-reduce)
-    la = ChattsLinearArgs{};
-    la.a = d->b.attn; la.w = lw.o; la.w_tiled = lw.o_t; la.m = t; la.n = H; la.k = c.n_q * kHeadDim;
-    la.lda = la.k; la.ldw = la.k; la.ldc = H;
-    la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-    if (t == 1) {
-      la.w8 = lw.o8; la.w8_scale = lw.o8_scale; la.ldw8 = la.k; la.w8_format = d->cfg.w8_format;
-      la.w4 = lw.o4; la.w4_sz = lw.o4_sz; la.ldw4 = la.k / 2; la.w4_group = lw.w4_group;
-    } else if (attn_out_planes) {              // written by the attention kernel
-      la.a = nullptr; la.a_hi = d->b.planes_hi; la.a_lo = d->b.planes_lo; la.ld_planes = la.k;
-    } else if (planes_path(d, t, la.k)) {      // the VALU attention kernel writes float32: split it
-      if ((rc = chatts_split_bf16x2(d->b.attn, t, la.k, la.k, d->b.planes_hi, d->b.planes_lo, la.k, stream)) != 0) return rc;
-      la.a_hi = d->b.planes_hi; la.a_lo = d->b.planes_lo; la.ld_planes = la.k;
-    }
-    d->tp_fused = false;
-    if (tp && t == 1 && d->fuse_tp && d->tp && !la.w4) {      // x += sum over the ranks, inside the GEMV launch (ChattsLinearArgs.tp_reduce)
-      la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID; la.tp_reduce = d->tp;
-      d->tp_fused = true;
-    } else if (tp) { la.c = d->b.delta; la.epilogue = CHATTS_EPI_NONE; }
-    else { la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID; }
-    request_post_norm(d, &la, lw.post_norm, false);
-    return chatts_linear(&la, stream);
-  }
-  // part 1: RMSNorm -> gate_up + SwiGLU -> down (+ residual / partial)
-  la = ChattsLinearArgs{};
-  la.w = lw.gate_up; la.w_tiled = lw.gate_up_t; la.c = d->b.act; la.m = t; la.n = 2 * c.inter; la.k = H;
-  la.lda = H; la.ldw = H; la.ldc = c.inter; la.epilogue = CHATTS_EPI_SWIGLU;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  if (t == 1) {
-    la.a = d->b.x; la.norm_w = lw.post_norm; la.norm_eps = c.rms_eps;
-    la.w8 = lw.gate_up8; la.w8_scale = lw.gate_up8_scale; la.ldw8 = H; la.w8_format = d->cfg.w8_format;
-    la.w4 = lw.gate_up4; la.w4_sz = lw.gate_up4_sz; la.ldw4 = H / 2; la.w4_group = lw.w4_group;
-  } else {
-    if ((rc = norm_into(d, lw.post_norm, &la, stream)) != 0) return rc;
-  }
-  const bool act_planes = t > 1 && planes_path(d, t, c.inter);   // SwiGLU output goes straight into down_proj's operand format
-  if (act_planes) { la.c = nullptr; la.c_hi = d->b.planes2_hi; la.c_lo = d->b.planes2_lo; la.ld_cplanes = c.inter; }
-  if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-  la = ChattsLinearArgs{};
-  la.a = d->b.act; la.w = lw.down; la.w_tiled = lw.down_t; la.m = t; la.n = H; la.k = c.inter;
-  la.lda = c.inter; la.ldw = c.inter; la.ldc = H;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  if (t == 1) {
-    la.w8 = lw.down8; la.w8_scale = lw.down8_scale; la.ldw8 = c.inter; la.w8_format = d->cfg.w8_format;
-    la.w4 = lw.down4; la.w4_sz = lw.down4_sz; la.ldw4 = c.inter / 2; la.w4_group = lw.w4_group;
-  }
-  if (act_planes) { la.a = nullptr; la.a_hi = d->b.planes2_hi; la.a_lo = d->b.planes2_lo; la.ld_planes = c.inter; }
-  d->tp_fused = false;
-  if (tp && t == 1 && d->fuse_tp && d->tp && !la.w4) {
-    la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID; la.tp_reduce = d->tp;
-    d->tp_fused = true;
-  } else if (tp) { la.c = d->b.delta; la.epilogue = CHATTS_EPI_NONE; }
-  else { la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID; }
-  request_post_norm(d, &la, layer + 1 < c.n_layers ? d->layers[layer + 1].input_norm : nullptr, false);
-  return chatts_linear(&la, stream);
+  return layer_half(d, layer, part, Rows{Rows::SEQ, t, pos0, pos0_dev, n_splits, nullptr, 0}, stream);
 }
 
 extern "C" int chatts_decoder_layer_part_add(ChattsDecoder* d, int add_delta, int layer, int part, int t, int pos0,
@@ -674,6 +856,9 @@ extern "C" int chatts_decoder_layer_part_add(ChattsDecoder* d, int add_delta, in
   return chatts_decoder_layer_part(d, layer, part, t, pos0, pos0_dev, n_splits, stream);
 }
 
+// rows of a batched call: cache slots 0 .. batch - 1 (bounded by max_batch), or inside a speculative step its R verify rows
+static int max_rows_batched(const ChattsDecoder* d) { return d->spec_rows > 0 ? d->spec_rows : max_batch(d); }
+
 // Batched decode: `batch` sequences advance one token each.  Row b of x / qkv / attn /
 // act belongs to sequence b (cache slot b, position pos_dev[b]).  The projections run as M = batch GEMMs (bf16x2
 // MFMA, weights streamed once for the whole batch); attention runs per sequence on its own cache.
@@ -681,98 +866,74 @@ extern "C" int chatts_decoder_layer_part_batched(ChattsDecoder* d, int layer, in
                                                  const int32_t* pos_dev, int n_splits, chatts_stream_t stream) {
   CHATTS_REQUIRE(d && layer >= 0 && layer < d->cfg.n_layers && (part == 0 || part == 1) && pos_dev, CHATTS_E_BADARG,
                  "decoder_layer_part_batched: bad arguments");
-  const int maxb = d->spec_rows > 0 ? d->spec_rows : (d->b.max_batch > 0 ? d->b.max_batch : 1);      // (max_batch guards cache slots)
+  const int maxb = max_rows_batched(d);      // (max_batch guards cache slots)
   CHATTS_REQUIRE(batch >= 1 && batch <= maxb && batch <= d->b.t_max, CHATTS_E_SHAPE,
                  "decoder_layer_part_batched: batch %d exceeds max_batch %d", batch, maxb);
-  StageRange stage(part == 0 ? "chatts.layer.attn" : "chatts.layer.mlp");
-  const ChattsDecoderConfig& c = d->cfg;
-  const ChattsLayerWeights& lw = d->layers[layer];
-  const bool tp = c.tp_world > 1;
-  const int H = c.hidden;
-  int rc;
-  ChattsLinearArgs la;
-  if (part == 0) {
-    const int qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim;
-    la = ChattsLinearArgs{};
-    la.w = lw.qkv; la.w_tiled = lw.qkv_t; la.bias = lw.qkv_bias; la.c = d->b.qkv; la.m = batch; la.n = qkv_n; la.k = H;
-    la.lda = H; la.ldw = H; la.ldc = qkv_n; la.epilogue = CHATTS_EPI_NONE;
-    la.w8 = lw.qkv8; la.w8_scale = lw.qkv8_scale; la.ldw8 = H; la.w8_format = d->cfg.w8_format;
-    la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-    if ((rc = norm_into(d, lw.input_norm, &la, stream)) != 0) return rc;
-    if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-    ChattsKvCache kc = layer_cache(d, layer, d->spec_rows > 0 ? d->cur_seq : 0);
-    const bool attn_planes = planes_path(d, batch, c.n_q * kHeadDim, lw.o8 != nullptr);   // the combine writes o_proj's operand format
-    if (d->spec_rows > 0) {
-      if ((rc = attention_verify_impl(d->b.qkv, batch, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos_dev,
-                                      &kc, d->b.attn, attn_planes ? d->b.planes_hi : nullptr, attn_planes ? d->b.planes_lo : nullptr,
-                                      n_splits, d->b.workspace, d->b.workspace_bytes, stream)) != 0) return rc;
-    } else if ((rc = attention_decode_batched_impl(d->b.qkv, batch, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, 0,
-                                            pos_dev, &kc, seq_stride(d), d->b.attn, attn_planes ? d->b.planes_hi : nullptr,
-                                            attn_planes ? d->b.planes_lo : nullptr, n_splits, d->b.workspace, d->b.workspace_bytes,
-                                            stream)) != 0) return rc;
-    la = ChattsLinearArgs{};
-    la.a = d->b.attn; la.w = lw.o; la.w_tiled = lw.o_t; la.m = batch; la.n = H; la.k = c.n_q * kHeadDim;
-    la.lda = la.k; la.ldw = la.k; la.ldc = H;
-    la.w8 = lw.o8; la.w8_scale = lw.o8_scale; la.ldw8 = la.k; la.w8_format = d->cfg.w8_format;
-    la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-    if (attn_planes) { la.a = nullptr; la.a_hi = d->b.planes_hi; la.a_lo = d->b.planes_lo; la.ld_planes = la.k; }
-    d->tp_fused = false;
-    if (tp) { la.c = d->b.delta; la.epilogue = CHATTS_EPI_NONE; }
-    else { la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID; }
-    // The residual stream ping-pongs x -> xn (here) -> x (down_proj) inside a chained step, so that the post-norm epilogue may use
-    // several workgroups per row (they read resid columns other workgroups update: c must not alias resid).
-    d->x_in_xn = false;
-    if (!tp && d->chain && d->b.xn && batch <= 16 && planes_path(d, batch, H, lw.gate_up8 != nullptr)) {
-      la.c = d->b.xn;
-      d->x_in_xn = true;
-    }
-    request_post_norm(d, &la, lw.post_norm, lw.gate_up8 != nullptr);
-    if (d->x_in_xn && !la.post_norm_w) { la.c = d->b.x; d->x_in_xn = false; }      // not fused after all: the norm launch reads x
-    return chatts_linear(&la, stream);
-  }
-  la = ChattsLinearArgs{};
-  la.w = lw.gate_up; la.w_tiled = lw.gate_up_t; la.c = d->b.act; la.m = batch; la.n = 2 * c.inter; la.k = H;
-  la.lda = H; la.ldw = H; la.ldc = c.inter; la.epilogue = CHATTS_EPI_SWIGLU;
-  la.w8 = lw.gate_up8; la.w8_scale = lw.gate_up8_scale; la.ldw8 = H; la.w8_format = d->cfg.w8_format;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  if ((rc = norm_into(d, lw.post_norm, &la, stream)) != 0) return rc;
-  const bool act_planes = planes_path(d, batch, c.inter, lw.down8 != nullptr) && planes_path(d, batch, H, lw.gate_up8 != nullptr);
-  if (act_planes) { la.c = nullptr; la.c_hi = d->b.planes2_hi; la.c_lo = d->b.planes2_lo; la.ld_cplanes = c.inter; }
-  if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-  la = ChattsLinearArgs{};
-  la.a = d->b.act; la.w = lw.down; la.w_tiled = lw.down_t; la.m = batch; la.n = H; la.k = c.inter;
-  la.lda = c.inter; la.ldw = c.inter; la.ldc = H;
-  la.w8 = lw.down8; la.w8_scale = lw.down8_scale; la.ldw8 = c.inter; la.w8_format = d->cfg.w8_format;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  if (act_planes) { la.a = nullptr; la.a_hi = d->b.planes2_hi; la.a_lo = d->b.planes2_lo; la.ld_planes = c.inter; }
-  d->tp_fused = false;
-  if (tp) { la.c = d->b.delta; la.epilogue = CHATTS_EPI_NONE; }
-  else { la.c = d->b.x; la.resid = d->x_in_xn ? d->b.xn : d->b.x; la.epilogue = CHATTS_EPI_RESID; }
-  d->x_in_xn = false;
-  request_post_norm(d, &la, layer + 1 < c.n_layers ? d->layers[layer + 1].input_norm : d->w.final_norm,
-                    (layer + 1 < c.n_layers ? d->layers[layer + 1].qkv8 : d->w.lm_head8) != nullptr);
-  return chatts_linear(&la, stream);
+  return layer_half(d, layer, part, Rows{d->spec_rows > 0 ? Rows::VERIFY : Rows::SLOTS, batch, 0, pos_dev, n_splits, nullptr, 0}, stream);
 }
 
 // final norm + lm_head for rows 0 .. batch-1 of x (cache slots 0 .. batch-1) -> logits_all [batch, vocab_local]: the tail of a
 // batched step (compute_logits for a batch, chatts_vllm.py:603-610).  M = batch weight-streaming GEMM on this rank's vocabulary slice.
 extern "C" int chatts_decoder_logits_batched(ChattsDecoder* d, int batch, float* logits_all, chatts_stream_t stream) {
   CHATTS_REQUIRE(d && logits_all, CHATTS_E_BADARG, "decoder_logits_batched: null argument");
-  const int maxb = d->spec_rows > 0 ? d->spec_rows : (d->b.max_batch > 0 ? d->b.max_batch : 1);
+  const int maxb = max_rows_batched(d);
   CHATTS_REQUIRE(batch >= 1 && batch <= maxb && batch <= d->b.t_max, CHATTS_E_SHAPE, "decoder_logits_batched: batch %d exceeds max_batch %d",
                  batch, maxb);
-  const ChattsDecoderConfig& c = d->cfg;
-  ChattsLinearArgs la{};
-  la.w = d->w.lm_head; la.c = logits_all; la.m = batch; la.n = (int)c.vocab_local; la.k = c.hidden;
-  la.lda = c.hidden; la.ldw = c.hidden; la.ldc = (int)c.vocab_local; la.epilogue = CHATTS_EPI_NONE;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  la.w8 = d->w.lm_head8; la.w8_scale = d->w.lm_head8_scale; la.ldw8 = c.hidden; la.w8_format = d->cfg.w8_format;
-  int rc = norm_into(d, d->w.final_norm, &la, stream);      // binds planes a fused epilogue already wrote (d->normed), or launches the norm
-  d->normed = false; d->normed_q = false;
+  ChattsLinearArgs la = linear_args(d, proj(d, 0, LM_HEAD), batch, CHATTS_EPI_NONE, W8);
+  la.c = logits_all;
+  const int rc = norm_into(d, d->w.final_norm, &la, stream);      // binds planes a fused epilogue already wrote (d->normed), or launches the norm
   if (rc) return rc;
   return chatts_linear(&la, stream);
 }
 
+extern "C" int chatts_decoder_logits(ChattsDecoder* d, int row, chatts_stream_t stream) {
+  CHATTS_REQUIRE(d && row >= 0 && row < d->b.t_max, CHATTS_E_BADARG, "decoder_logits: bad row");
+  StageRange stage("chatts.logits");
+  ChattsLinearArgs la = linear_args(d, proj(d, 0, LM_HEAD), 1, CHATTS_EPI_NONE, W8);
+  la.c = d->b.logits;
+  norm_in_launch(d, d->b.x + (size_t)row * d->cfg.hidden, d->w.final_norm, &la);
+  return chatts_linear(&la, stream);
+}
+
+// ---- the layer loop --------------------------------------------------------------------------------------------------------------
+// Layers [first, last): half(layer, part) for part 0 and 1, each followed by sum() - the tensor-parallel sum of the half's partial
+// result into x (sum_bulk, sum_unless_fused), or nothing.  Stops at the first error and returns it.
+template <class Half, class Sum>
+static int run_layers(int first, int last, Half half, Sum sum) {
+  int rc = CHATTS_OK;
+  for (int l = first; l < last && rc == CHATTS_OK; ++l)
+    for (int part = 0; part < 2 && rc == CHATTS_OK; ++part)
+      if ((rc = half(l, part)) == CHATTS_OK) rc = sum();
+  return rc;
+}
+static int no_sum() { return CHATTS_OK; }
+
+// tensor parallel: can the [t, H] sums between the layer halves run as chatts_allreduce_bulk launches of the same call?
+static bool tp_bulk_ready(const ChattsDecoder* d, int t) {
+  return d->tp && chatts_tp_bulk_elems(d->tp) >= (int64_t)t * d->cfg.hidden;
+}
+#define CHATTS_REQUIRE_TP_BULK(d, t, name)                                                                                         \
+  CHATTS_REQUIRE((d)->cfg.tp_world == 1 || tp_bulk_ready((d), (t)), CHATTS_E_BADARG,                                                \
+                 name ": tp_world = %d needs an attached exchange whose bulk region holds t * hidden = %lld float32 (chatts_tp_buffer_bytes_bulk); " \
+                 "otherwise drive chatts_decoder_layer_part_add and all-reduce buffers.delta yourself", (d)->cfg.tp_world,          \
+                 (long long)(t) * (d)->cfg.hidden)
+// prefill chunks: x[0:t] += sum over the ranks of delta[0:t]
+static int sum_bulk(ChattsDecoder* d, int t, chatts_stream_t stream) {
+  if (d->cfg.tp_world <= 1) return CHATTS_OK;
+  return chatts_allreduce_bulk(d->tp, d->b.delta, d->b.x, (int64_t)t * d->cfg.hidden, stream);
+}
+// decode rows: x[0:rows] += sum over the ranks of delta[0:rows], unless the projection's own launch carried the exchange (d->tp_fused)
+static int sum_unless_fused(ChattsDecoder* d, int rows, chatts_stream_t stream) {
+  if (d->cfg.tp_world <= 1 || d->tp_fused) return CHATTS_OK;
+  return chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, (int64_t)rows * d->cfg.hidden, stream);
+}
+// layers [first, last) of one sequence's chunk of t rows at pos0
+static int run_chunk_layers(ChattsDecoder* d, int first, int last, int t, int pos0, chatts_stream_t stream) {
+  return run_layers(first, last, [&](int l, int part) { return chatts_decoder_layer_part(d, l, part, t, pos0, nullptr, 1, stream); },
+                    [&] { return sum_bulk(d, t, stream); });
+}
+
+// ---- the whole-pass entry points -------------------------------------------------------------------------------------------------
 // One greedy step for `batch` sequences (TP = 1): all layers, final norm + lm_head for every row, per-sequence
 // argmax (token / step / pos / out_tokens rows advance independently; pos saturates at max_ctx - 1).
 // logits_all: [batch, vocab_local] float32 scratch owned by the caller.
@@ -793,34 +954,13 @@ extern "C" int chatts_decoder_decode_step_batched(ChattsDecoder* d, int batch, i
   // use x between two steps) and ENDS with the per-sequence argmax
   if ((rc = chatts_embed_token_batched(token_dev, batch, d->w.embed, embed_offset(d), embed_rows(d), c.hidden, d->b.x,
                                        stream)) != 0) return rc;
-  d->chain = true;               // layers run back to back: a projection may write the next one's normed operand
-  d->normed = false; d->normed_q = false;
-  const int64_t nx = (int64_t)batch * c.hidden;
-  for (int l = 0; l < c.n_layers && rc == CHATTS_OK; ++l) {
-    rc = chatts_decoder_layer_part_batched(d, l, 0, batch, pos_dev, n_splits, stream);
-    if (tp && rc == CHATTS_OK && !d->tp_fused) rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, nx, stream);     // x += sum of the partial o_proj
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part_batched(d, l, 1, batch, pos_dev, n_splits, stream);
-    if (tp && rc == CHATTS_OK && !d->tp_fused) rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, nx, stream);     // ... and down_proj
-  }
-  d->chain = false;
-  if (rc) { d->normed = false; d->normed_q = false; return rc; }
+  Pass pass(d, /*chain=*/true);      // layers run back to back: a projection may write the next one's normed operand
+  rc = run_layers(0, c.n_layers, [&](int l, int part) { return chatts_decoder_layer_part_batched(d, l, part, batch, pos_dev, n_splits, stream); },
+                  [&] { return sum_unless_fused(d, batch, stream); });
+  if (rc) return rc;
   if ((rc = chatts_decoder_logits_batched(d, batch, logits_all, stream)) != 0) return rc;
   return chatts_decoder_select_tokens(d, logits_all, batch, c.vocab_local, token_dev, token_logit_dev, out_tokens, out_stride, step_dev,
                                       pos_dev, c.max_ctx - 1, nullptr, stream);
-}
-
-// tensor parallel: can the [t, H] sums between the layer halves run as chatts_allreduce_bulk launches of the same call?
-static bool tp_bulk_ready(const ChattsDecoder* d, int t) {
-  return d->tp && chatts_tp_bulk_elems(d->tp) >= (int64_t)t * d->cfg.hidden;
-}
-#define CHATTS_REQUIRE_TP_BULK(d, t, name)                                                                                         \
-  CHATTS_REQUIRE((d)->cfg.tp_world == 1 || tp_bulk_ready((d), (t)), CHATTS_E_BADARG,                                                \
-                 name ": tp_world = %d needs an attached exchange whose bulk region holds t * hidden = %lld float32 (chatts_tp_buffer_bytes_bulk); " \
-                 "otherwise drive chatts_decoder_layer_part_add and all-reduce buffers.delta yourself", (d)->cfg.tp_world,          \
-                 (long long)(t) * (d)->cfg.hidden)
-// x[0:t] += sum over the ranks of delta[0:t]
-static int tp_sum_into_x(ChattsDecoder* d, int t, chatts_stream_t stream) {
-  return chatts_allreduce_bulk(d->tp, d->b.delta, d->b.x, (int64_t)t * d->cfg.hidden, stream);
 }
 
 extern "C" int chatts_decoder_prefill(ChattsDecoder* d, int t, int pos0, chatts_stream_t stream) {
@@ -828,68 +968,22 @@ extern "C" int chatts_decoder_prefill(ChattsDecoder* d, int t, int pos0, chatts_
   CHATTS_REQUIRE(t >= 1 && t <= d->b.t_max, CHATTS_E_SHAPE, "decoder_prefill: t=%d exceeds buffers (%d)", t, d->b.t_max);
   CHATTS_REQUIRE_TP_BULK(d, t, "decoder_prefill");
   StageRange stage("chatts.prefill");
-  const bool tp = d->cfg.tp_world > 1;
-  d->chain = true;
-  d->normed = false; d->normed_q = false;
-  int rc = CHATTS_OK;
-  for (int l = 0; l < d->cfg.n_layers && rc == CHATTS_OK; ++l) {
-    rc = chatts_decoder_layer_part(d, l, 0, t, pos0, nullptr, 1, stream);
-    if (tp && rc == CHATTS_OK) rc = tp_sum_into_x(d, t, stream);
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part(d, l, 1, t, pos0, nullptr, 1, stream);
-    if (tp && rc == CHATTS_OK) rc = tp_sum_into_x(d, t, stream);
-  }
-  d->chain = false;
-  d->normed = false; d->normed_q = false;
-  return rc;
+  Pass pass(d, /*chain=*/true);
+  return run_chunk_layers(d, 0, d->cfg.n_layers, t, pos0, stream);
 }
 
 // The LAST layer of a prefill whose only consumers are the next token and the KV cache: K / V of every row are needed
 // (cache), everything else only for the last row.  So: RMSNorm + qkv GEMM + RoPE / cache write for all t rows as usual, then
 // the last row alone is attended (t = 1 against the cache), moved to row 0 of the residual stream and taken through o_proj
 // and the MLP as weight-streaming GEMVs.  Saves one layer's attention + o / gate_up / down GEMMs (~0.9 of 44 ms at the
-// benchmark prompt).  The result lives in row 0 of x (rows 1.. are stale).
+// benchmark prompt).  The result lives in row 0 of x (rows 1.. are stale).  (f16q mode: this layer runs the default kernels.)
 static int layer_last_row(ChattsDecoder* d, int layer, int t, int pos0, chatts_stream_t stream) {
-  d->normed_q = false;      // (f16q mode: the last layer runs the default kernels)
-  const ChattsDecoderConfig& c = d->cfg;
-  const ChattsLayerWeights& lw = d->layers[layer];
-  const int H = c.hidden, qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim;
-  int rc;
-  ChattsLinearArgs la{};
-  la.w = lw.qkv; la.w_tiled = lw.qkv_t; la.bias = lw.qkv_bias; la.c = d->b.qkv; la.m = t; la.n = qkv_n; la.k = H;
-  la.lda = H; la.ldw = H; la.ldc = qkv_n; la.epilogue = CHATTS_EPI_NONE;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  if ((rc = norm_into(d, lw.input_norm, &la, stream)) != 0) return rc;
-  if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-  ChattsKvCache kc = layer_cache(d, layer, d->cur_seq);
-  if ((rc = chatts_rope_kv_write(d->b.qkv, t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, pos0,
-                                 nullptr, &kc, stream)) != 0) return rc;
-  // one query row against pos0 + t keys: spread the 64-key tiles over up to 16 workgroups per kv head (one workgroup walking 800
-  // keys alone took 137 us in the round-2 trace)
-  int ks = (pos0 + t + 63) / 64;
-  if (ks > 16) ks = 16;
-  if (ks < 1 || chatts_attn_workspace(1, c.n_q, ks) > d->b.workspace_bytes) ks = 1;
-  if ((rc = chatts_attention(d->b.qkv + (size_t)(t - 1) * qkv_n, 1, c.n_q, c.n_kv, pos0 + t - 1, nullptr, &kc, d->b.attn, ks,
-                             d->b.workspace, d->b.workspace_bytes, stream)) != 0) return rc;
-  if (t > 1) {
-    const hipError_t e = hipMemcpyAsync(d->b.x, d->b.x + (size_t)(t - 1) * H, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice,
-                                        as_stream(stream));
-    CHATTS_REQUIRE(e == hipSuccess, CHATTS_E_LAUNCH, "prefill_last: row copy: %s", hipGetErrorString(e));
-  }
-  la = ChattsLinearArgs{};
-  la.a = d->b.attn; la.w = lw.o; la.w_tiled = lw.o_t; la.m = 1; la.n = H; la.k = c.n_q * kHeadDim; la.lda = la.k; la.ldw = la.k; la.ldc = H;
-  la.w8 = lw.o8; la.w8_scale = lw.o8_scale; la.ldw8 = la.k; la.w8_format = d->cfg.w8_format;
-  la.w4 = lw.o4; la.w4_sz = lw.o4_sz; la.ldw4 = la.k / 2; la.w4_group = lw.w4_group;
-  la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID;
-  const bool tp = c.tp_world > 1;
-  if (tp && !la.w4) la.tp_reduce = d->tp;                  // row 0 of x += the sum over the ranks, inside the GEMV launch
-  else if (tp) { la.c = d->b.delta; la.resid = nullptr; la.epilogue = CHATTS_EPI_NONE; }
-  if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-  if (tp && !la.tp_reduce && (rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, H, stream)) != 0) return rc;
-  d->fuse_tp = tp;
+  int rc = layer_half(d, layer, 0, Rows{Rows::LAST, t, pos0, nullptr, 1, nullptr, 0}, stream);
+  if (rc) return rc;
+  d->fuse_tp = d->cfg.tp_world > 1;      // for this half only: the exchange rides in the down_proj GEMV, as in a decode step
   rc = chatts_decoder_layer_part(d, layer, 1, 1, 0, nullptr, 1, stream);      // MLP on row 0: the decode path's GEMVs
   d->fuse_tp = false;
-  if (rc == CHATTS_OK && tp && !d->tp_fused) rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, H, stream);
-  return rc;
+  return rc == CHATTS_OK ? sum_unless_fused(d, 1, stream) : rc;
 }
 
 extern "C" int chatts_decoder_prefill_last(ChattsDecoder* d, int t, int pos0, chatts_stream_t stream) {
@@ -897,99 +991,30 @@ extern "C" int chatts_decoder_prefill_last(ChattsDecoder* d, int t, int pos0, ch
   CHATTS_REQUIRE(t >= 1 && t <= d->b.t_max, CHATTS_E_SHAPE, "decoder_prefill_last: t=%d exceeds buffers (%d)", t, d->b.t_max);
   CHATTS_REQUIRE_TP_BULK(d, t, "decoder_prefill_last");
   StageRange stage("chatts.prefill_last");
-  const bool tp = d->cfg.tp_world > 1;
-  d->chain = true;
-  d->normed = false; d->normed_q = false;
-  int rc = CHATTS_OK;
   const int L = d->cfg.n_layers;
-  for (int l = 0; l + 1 < L && rc == CHATTS_OK; ++l) {
-    rc = chatts_decoder_layer_part(d, l, 0, t, pos0, nullptr, 1, stream);
-    if (tp && rc == CHATTS_OK) rc = tp_sum_into_x(d, t, stream);
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part(d, l, 1, t, pos0, nullptr, 1, stream);
-    if (tp && rc == CHATTS_OK) rc = tp_sum_into_x(d, t, stream);
+  Pass pass(d, /*chain=*/true);
+  int rc = run_chunk_layers(d, 0, L - 1, t, pos0, stream);
+  if (rc == CHATTS_OK && d->prefill_fp8 && t >= kFp8MinRows) {      // speed mode: the final layer at full width too, then the last row moves to row 0
+    rc = run_chunk_layers(d, L - 1, L, t, pos0, stream);
+    if (rc == CHATTS_OK) rc = last_row_to_row0(d, t, stream);
+  } else if (rc == CHATTS_OK) {
+    rc = layer_last_row(d, L - 1, t, pos0, stream);
   }
-  if (rc == CHATTS_OK && d->prefill_fp8 && t >= 16) {      // speed mode: the final layer at full width too, then the last row moves to row 0
-    rc = chatts_decoder_layer_part(d, L - 1, 0, t, pos0, nullptr, 1, stream);
-    if (tp && rc == CHATTS_OK) rc = tp_sum_into_x(d, t, stream);
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part(d, L - 1, 1, t, pos0, nullptr, 1, stream);
-    if (tp && rc == CHATTS_OK) rc = tp_sum_into_x(d, t, stream);
-    if (rc == CHATTS_OK && t > 1) {
-      const hipError_t e = hipMemcpyAsync(d->b.x, d->b.x + (size_t)(t - 1) * d->cfg.hidden, (size_t)d->cfg.hidden * sizeof(float),
-                                          hipMemcpyDeviceToDevice, as_stream(stream));
-      if (e != hipSuccess) { set_error("prefill_last: row copy: %s", hipGetErrorString(e)); rc = CHATTS_E_LAUNCH; }
-    }
-  } else if (rc == CHATTS_OK) rc = layer_last_row(d, L - 1, t, pos0, stream);
-  d->chain = false;
-  d->normed = false; d->normed_q = false;
   // the last row's o_proj / down_proj carried their exchange without advancing the device-side call counter (host-counted epochs):
-  // settle it here, so that whatever runs next on this communicator - a replayed decode graph above all - starts from a flushed count
-  if (tp && d->tp) { const int frc = chatts_tp_flush_epochs(d->tp, stream); if (rc == CHATTS_OK) rc = frc; }
+  // settle it here, always, so that whatever runs next on this communicator - a replayed decode graph above all - starts from a flushed count
+  if (d->cfg.tp_world > 1 && d->tp) { const int frc = chatts_tp_flush_epochs(d->tp, stream); if (rc == CHATTS_OK) rc = frc; }
   return rc;
 }
 
 // Packed multi-prompt prefill: the rows of several prompts (or of their not-yet-cached tails) sit
 // back to back in x; everything row-wise - norms, the four projections, SwiGLU, residuals - runs ONCE over all rows (one big-M
 // GEMM instead of one ragged small-M GEMM per prompt), only RoPE / cache write / attention run per segment, each against
-// its own cache slot and positions.
-static int layer_part0_packed(ChattsDecoder* d, int layer, int t, const ChattsPrefillSegment* segs, int n_segs,
-                              chatts_stream_t stream) {
-  const ChattsDecoderConfig& c = d->cfg;
-  const ChattsLayerWeights& lw = d->layers[layer];
-  const int H = c.hidden, qkv_n = (c.n_q + 2 * c.n_kv) * kHeadDim, na = c.n_q * kHeadDim;
-  int rc;
-  d->normed_q = false;      // (f16q mode: this half runs the default kernels and is about to overwrite planes 0 - the next MLP half recomputes its norm)
-  const bool f8 = d->prefill_fp8 && t >= 16;          // speed mode: qkv and o_proj as fp8 x fp8 GEMMs (layer_part_fp8's arithmetic)
-  ChattsLinearArgs la{};
-  if (f8) {
-    d->normed = false; d->normed_q = false;
-    uint8_t* a8 = reinterpret_cast<uint8_t*>(d->b.planes_hi);
-    if ((rc = chatts_quantize_rows_fp8(d->b.x, t, H, H, lw.input_norm, c.rms_eps, a8, H, d->b.xn, stream)) != 0) return rc;
-    ChattsLinearFp8Args f{};
-    f.a8 = a8; f.a_scale = d->b.xn; f.w8 = lw.qkv8; f.w_scale = lw.qkv8_scale; f.bias = lw.qkv_bias; f.c = d->b.qkv;
-    f.m = t; f.n = qkv_n; f.k = H; f.lda8 = H; f.ldw8 = H; f.ldc = qkv_n; f.epilogue = CHATTS_EPI_NONE;
-    if ((rc = chatts_linear_fp8(&f, stream)) != 0) return rc;
-  } else {
-    la.w = lw.qkv; la.w_tiled = lw.qkv_t; la.bias = lw.qkv_bias; la.c = d->b.qkv; la.m = t; la.n = qkv_n; la.k = H;
-    la.lda = H; la.ldw = H; la.ldc = qkv_n; la.epilogue = CHATTS_EPI_NONE;
-    la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-    if ((rc = norm_into(d, lw.input_norm, &la, stream)) != 0) return rc;
-    if ((rc = chatts_linear(&la, stream)) != 0) return rc;
-  }
-  for (int i = 0; i < n_segs; ++i) {
-    const ChattsPrefillSegment& sg = segs[i];
-    ChattsKvCache kc = layer_cache(d, layer, sg.slot);
-    float* q = d->b.qkv + (size_t)sg.row0 * qkv_n;
-    if ((rc = chatts_rope_kv_write(q, sg.t, c.n_q, c.n_kv, lw.q_norm, lw.k_norm, c.rms_eps, d->w.cos_tab, d->w.sin_tab, sg.pos0,
-                                   nullptr, &kc, stream)) != 0) return rc;
-    const int ks = 1;
-    if ((rc = attention_impl(q, sg.t, c.n_q, c.n_kv, sg.pos0, nullptr, &kc, d->b.attn + (size_t)sg.row0 * na, nullptr, nullptr, ks,
-                             d->b.workspace, d->b.workspace_bytes, stream)) != 0) return rc;
-  }
-  if (f8) {
-    uint8_t* b8 = reinterpret_cast<uint8_t*>(d->b.planes_lo);
-    float* sb = d->b.xn + d->b.t_max;
-    if ((rc = chatts_quantize_rows_fp8(d->b.attn, t, na, na, nullptr, 0.f, b8, na, sb, stream)) != 0) return rc;
-    ChattsLinearFp8Args f{};
-    f.a8 = b8; f.a_scale = sb; f.w8 = lw.o8; f.w_scale = lw.o8_scale; f.m = t; f.n = H; f.k = na; f.lda8 = na; f.ldw8 = na; f.ldc = H;
-    f.c = d->b.x; f.resid = d->b.x; f.epilogue = CHATTS_EPI_RESID;
-    return chatts_linear_fp8(&f, stream);
-  }
-  la = ChattsLinearArgs{};
-  la.a = d->b.attn; la.w = lw.o; la.w_tiled = lw.o_t; la.m = t; la.n = H; la.k = na; la.lda = na; la.ldw = na; la.ldc = H;
-  la.workspace = d->b.workspace; la.workspace_bytes = d->b.workspace_bytes;
-  if (t > 1 && planes_path(d, t, na)) {
-    if ((rc = chatts_split_bf16x2(d->b.attn, t, na, na, d->b.planes_hi, d->b.planes_lo, na, stream)) != 0) return rc;
-    la.a_hi = d->b.planes_hi; la.a_lo = d->b.planes_lo; la.ld_planes = na;
-  }
-  la.c = d->b.x; la.resid = d->b.x; la.epilogue = CHATTS_EPI_RESID;
-  request_post_norm(d, &la, lw.post_norm, false);
-  return chatts_linear(&la, stream);
-}
-
+// its own cache slot and positions (Rows::PACKED: ks = 1 and no attention-written planes).  Speed mode: qkv and o_proj as fp8 x fp8
+// GEMMs like any chunk; f16q mode: the attention half runs the default kernels, the MLP half is a chunk's.
 extern "C" int chatts_decoder_prefill_packed(ChattsDecoder* d, const ChattsPrefillSegment* segs, int n_segs, chatts_stream_t stream) {
   CHATTS_REQUIRE(d && segs && n_segs >= 1, CHATTS_E_BADARG, "decoder_prefill_packed: bad arguments");
   CHATTS_REQUIRE(d->cfg.tp_world == 1, CHATTS_E_BADARG, "decoder_prefill_packed: tensor_parallel_size 1 only");
-  const int maxb = d->b.max_batch > 0 ? d->b.max_batch : 1;
+  const int maxb = max_batch(d);
   int t = 0;
   for (int i = 0; i < n_segs; ++i) {
     const ChattsPrefillSegment& sg = segs[i];
@@ -1002,28 +1027,11 @@ extern "C" int chatts_decoder_prefill_packed(ChattsDecoder* d, const ChattsPrefi
   }
   CHATTS_REQUIRE(t <= d->b.t_max, CHATTS_E_SHAPE, "decoder_prefill_packed: %d rows exceed buffers (%d)", t, d->b.t_max);
   StageRange stage("chatts.prefill_packed");
-  d->chain = true;
-  d->normed = false; d->normed_q = false;
-  int rc = CHATTS_OK;
-  for (int l = 0; l < d->cfg.n_layers && rc == CHATTS_OK; ++l) {
-    rc = layer_part0_packed(d, l, t, segs, n_segs, stream);
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part(d, l, 1, t, 0, nullptr, 1, stream);
-  }
-  d->chain = false;
-  d->normed = false; d->normed_q = false;
-  return rc;
-}
-
-extern "C" int chatts_decoder_logits(ChattsDecoder* d, int row, chatts_stream_t stream) {
-  CHATTS_REQUIRE(d && row >= 0 && row < d->b.t_max, CHATTS_E_BADARG, "decoder_logits: bad row");
-  StageRange stage("chatts.logits");
-  const ChattsDecoderConfig& c = d->cfg;
-  ChattsLinearArgs la{};
-  la.a = d->b.x + (size_t)row * c.hidden; la.w = d->w.lm_head; la.c = d->b.logits;
-  la.m = 1; la.n = (int)c.vocab_local; la.k = c.hidden; la.lda = c.hidden; la.ldw = c.hidden; la.ldc = (int)c.vocab_local;
-  la.epilogue = CHATTS_EPI_NONE; la.norm_w = d->w.final_norm; la.norm_eps = c.rms_eps;
-  la.w8 = d->w.lm_head8; la.w8_scale = d->w.lm_head8_scale; la.ldw8 = c.hidden; la.w8_format = d->cfg.w8_format;
-  return chatts_linear(&la, stream);
+  Pass pass(d, /*chain=*/true);
+  const Rows packed{Rows::PACKED, t, 0, nullptr, 1, segs, n_segs};
+  return run_layers(0, d->cfg.n_layers, [&](int l, int part) {
+    return part == 0 ? layer_half(d, l, 0, packed, stream) : chatts_decoder_layer_part(d, l, 1, t, 0, nullptr, 1, stream);
+  }, no_sum);
 }
 
 extern "C" int chatts_decoder_decode_step(ChattsDecoder* d, int32_t* pos_dev, int32_t* step_dev, int64_t* token_dev,
@@ -1036,18 +1044,13 @@ extern "C" int chatts_decoder_decode_step(ChattsDecoder* d, int32_t* pos_dev, in
   CHATTS_REQUIRE(!tp || chatts_tp_pending(d->tp) == 0, CHATTS_E_BADARG, "decode_step: the exchange has %d collectives whose epochs were never settled "
                  "(chatts_tp_flush_epochs): a step enqueued or captured now would reuse their epochs", tp ? chatts_tp_pending(d->tp) : 0);
   int rc;
-  const int H = d->cfg.hidden;
-  // Tensor parallel: the two exchanges of a layer ride in the o_proj / down_proj GEMV launches (6 launches per layer instead of 8;
-  // CHATTS_TP_FUSE=0 keeps the stand-alone chatts_allreduce kernels: same bits - tests/test_gpu_tp_p2p.py)
-  d->fuse_tp = tp && opt_get(OPT_TP_FUSE, 1) != 0;
-  rc = CHATTS_OK;
-  for (int l = 0; l < d->cfg.n_layers && rc == CHATTS_OK; ++l) {
-    rc = chatts_decoder_layer_part(d, l, 0, 1, 0, pos_dev, n_splits, stream);
-    if (rc == CHATTS_OK && tp && !d->tp_fused) rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, H, stream);    // x += sum of the partial o_proj
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part(d, l, 1, 1, 0, pos_dev, n_splits, stream);
-    if (rc == CHATTS_OK && tp && !d->tp_fused) rc = chatts_allreduce(d->tp, d->b.delta, d->b.x, d->b.x, H, stream);    // ... and down_proj
+  {
+    // Tensor parallel: the two exchanges of a layer ride in the o_proj / down_proj GEMV launches (6 launches per layer instead of 8;
+    // CHATTS_TP_FUSE=0 keeps the stand-alone chatts_allreduce kernels: same bits - tests/test_gpu_tp_p2p.py)
+    Pass pass(d, /*chain=*/false, /*spec_rows=*/0, /*fuse_tp=*/tp && opt_get(OPT_TP_FUSE, 1) != 0);
+    rc = run_layers(0, d->cfg.n_layers, [&](int l, int part) { return chatts_decoder_layer_part(d, l, part, 1, 0, pos_dev, n_splits, stream); },
+                    [&] { return sum_unless_fused(d, 1, stream); });
   }
-  d->fuse_tp = false;
   if (rc) {      // a refused launch part-way: settle the epochs of the exchange-carrying GEMVs that WERE issued (every rank fails alike)
     if (tp) (void)chatts_tp_flush_epochs(d->tp, stream);
     return rc;
@@ -1076,7 +1079,7 @@ extern "C" int chatts_decoder_spec_step(ChattsDecoder* d, const ChattsSpecArgs* 
   const int R = a->k + 1;
   CHATTS_REQUIRE(R <= d->b.t_max && R < c.max_ctx, CHATTS_E_SHAPE, "decoder_spec_step: %d rows exceed the buffers (%d) or the context", R,
                  d->b.t_max);
-  int ns = a->n_splits < 1 ? 1 : (a->n_splits > 64 ? 64 : a->n_splits);
+  int ns = a->n_splits < 1 ? 1 : (a->n_splits > 64 ? 64 : a->n_splits);      // clamped before anything is enqueued
   while (ns > 1 && chatts_attn_workspace(R, c.n_q, ns) > d->b.workspace_bytes) ns /= 2;      // fewer, longer tile slots: the partials must fit
   CHATTS_REQUIRE(d->b.workspace && chatts_attn_workspace(R, c.n_q, ns) <= d->b.workspace_bytes, CHATTS_E_WORKSPACE,
                  "decoder_spec_step: the workspace does not hold the attention partials of %d rows", R);
@@ -1087,18 +1090,9 @@ extern "C" int chatts_decoder_spec_step(ChattsDecoder* d, const ChattsSpecArgs* 
       (rc = chatts_spec_propose(a->pos_dev, a->hist, c.max_ctx, a->k, a->ngram_min, a->ngram_max, vocab, a->draft, a->spec_tokens, stream)) != 0)
     return rc;
   if ((rc = chatts_embed_token_batched(a->spec_tokens, R, d->w.embed, embed_offset(d), embed_rows(d), c.hidden, d->b.x, stream)) != 0) return rc;
-  d->chain = true;
-  d->normed = false; d->normed_q = false;
-  d->spec_rows = R;
-  rc = CHATTS_OK;
-  for (int l = 0; l < c.n_layers && rc == CHATTS_OK; ++l) {
-    rc = chatts_decoder_layer_part_batched(d, l, 0, R, a->pos_dev, ns, stream);
-    if (rc == CHATTS_OK) rc = chatts_decoder_layer_part_batched(d, l, 1, R, a->pos_dev, ns, stream);
-  }
-  d->chain = false;
+  Pass pass(d, /*chain=*/true, /*spec_rows=*/R);      // the batched halves and the logits take R verify rows of the selected sequence
+  rc = run_layers(0, c.n_layers, [&](int l, int part) { return chatts_decoder_layer_part_batched(d, l, part, R, a->pos_dev, ns, stream); }, no_sum);
   if (rc == CHATTS_OK) rc = chatts_decoder_logits_batched(d, R, a->logits, stream);
-  d->spec_rows = 0;
-  d->normed = false; d->normed_q = false;
   if (rc) return rc;
   // per-row argmax without side effects (the split-K / attention workspace is idle here)
   if ((rc = chatts::argmax_batched_scratch(a->logits, R, c.vocab_local, c.vocab_local, c.vocab_offset, a->argmax, nullptr, nullptr, 0, nullptr,

@@ -149,7 +149,7 @@ def test_f16q_prefill_mode_matches_oracle(preset, lengths):
 
 def test_f16q_mode_with_packed_multi_prompt_prefill_matches_oracle():
     """precision='f16q' under continuous batching: several prompts prefilled in ONE packed pass of > 96 rows - the attention half of a layer
-    runs the default kernels per segment (layer_part0_packed), the MLP half the f16q projections, and the plane buffers change their type in
+    runs the default kernels per segment (attn_half on Rows::PACKED), the MLP half the f16q projections, and the plane buffers change their type in
     between: every request must still produce the oracle's tokens (a stale 'planes already normed' flag across that boundary would not)."""
     from chatts_amd import config as cfgmod, synth
     from chatts_amd.modeling import ChatTSForCausalLM
