@@ -1,17 +1,19 @@
-// gemv.hip - batch-1 decode projections: y[N] = epilogue(W[N,K] . x[K]),  W bf16 streamed from HBM.
+// gemv.hip - batch-1 decode projections: y[N] = epilogue(W[N,K] . x[K]),  W streamed from HBM as bf16, 8-bit (fp8 / int8) or 4-bit codes.
 //
-// This kernel sets generated tokens/s: every decode step streams all decoder weights once
-// (27.98 GB for ChatTS-14B), so it is HBM-bound by construction.  It follows the guide's
-// "GEMV / M<=16 decode weights" rule: weights go straight to VGPRs as non-temporal 16-byte loads,
-// many loads in flight per lane, no LDS round trip for the streamed operand.
+// This file sets generated tokens/s: every decode step streams all decoder weights once (27.98 GB for ChatTS-14B in bf16), so it is
+// HBM-bound by construction.  It follows the guide's "GEMV / M<=16 decode weights" rule: weights go straight to VGPRs as non-temporal
+// loads, many loads in flight per lane, no LDS round trip for the streamed operand.
 //
-// Geometry: one wave per group of 2 rows over the whole K; the small, re-used operand x (20-55 KB f32) is
-// staged once per workgroup in LDS (4-16 waves share it), permuted so that each lane's two 16-byte reads
-// per 512-element chunk are lane-linear (conflict-free ds_read_b128); 2 rows x 2 chunks = 4 independent
-// 16-byte weight loads in flight per lane, 16-32 waves per CU.  A K-split variant that kept x in registers
-// and issued 12-14 loads per lane was measured and lost on every shape (tools/gemv_sweep.py).
-// Arithmetic: bf16 -> f32 widening is exact and x is f32, so every product is exact in the f32 FMA;
-// only the summation order differs from the CPU oracle (parity budget: 1e-3 relative on logits).
+// One prologue (gemv_stage_x), one stream loop (gemv_stream) and one task loop (gemv_whole_k) serve three weight formats (FmtBf16,
+// FmtW8, FmtInt4: what differs between them is written down once, in those structs); the __global__ kernels are entry points that name
+// a format.  Geometry: one wave per group of ROWS rows over the whole K; the small, re-used operand x (20-55 KB f32) is staged once per
+// workgroup in LDS (4-16 waves share it), permuted so that each lane's 16-byte reads of a chunk are lane-linear (conflict-free
+// ds_read_b128); ROWS x UNR independent weight loads in flight per lane, 16-32 waves per CU.  A row is summed by ONE wave in a fixed
+// lane and chunk order whatever the geometry, with or without the exchange of tp_reduce.  gemv_ksplit_kernel (bf16, shard-sized
+// projections) shares a row between several waves and is the one exception.  A variant that kept x in registers and issued 12-14
+// loads per lane was measured and lost on every shape (tools/gemv_sweep.py).
+// Arithmetic: every weight widens exactly to f32 and x is f32, so every product is exact in the f32 FMA; only the summation order
+// differs from the CPU oracle (parity budget: 1e-3 relative on logits).  (The 4-bit form meets x as a bf16 hi + lo pair: FmtInt4.)
 // Fusions: RMSNorm of x in the prologue (Qwen2RMSNorm.forward), bias, residual add, SwiGLU.
 #include "common.h"
 #include "gemv_common.h"
@@ -126,196 +128,42 @@ __device__ __forceinline__ void gemv_epilogue(const GemvParams& p, int task, int
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// x in LDS, one wave per row group over the whole K.  blockDim = 64 * NW (NW = 4, 8 or 16 waves share one
-// staged copy of x); ROWS x UNR 16-byte weight loads in flight per lane.
-// ------------------------------------------------------------------------------------------------
-template <int ROWS, int UNR, int EPI, bool NORM>
-__global__ __launch_bounds__(1024) void gemv_ldsx_kernel(GemvParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  f32x4* xs4 = reinterpret_cast<f32x4*>(smem);            // permuted x: [chunk][half][lane] float4
-  float* red = reinterpret_cast<float*>(smem) + (size_t)((p.k + 511) / 512) * 512;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nthreads = blockDim.x, nw = nthreads >> 6;
-  const int K = p.k;
-  const int nchunks = (K + 511) >> 9;
-  uint32_t epoch = 0;
-  if (EPI == kEpiResidTp) epoch = tp_epoch(p.tp);
+// ---- the three weight formats ----------------------------------------------------------------------------------------------------
+// A format supplies what differs between the kernels: the chunk (1 << kShift elements of K: what 64 lanes cover with one load each),
+// the LDS store of one staged float4 of x, a row's state, the zero-filled load, a lane's x fragment of a chunk, the dot of one load, the
+// scalar handed to wave_sum and what is applied to the sum.  The FMA order inside each dot function is part of the result's bits.
 
-  float rstd = 1.f;
-  if (NORM) {
-    float ss = 0.f;
-    for (int k4 = tid * 4; k4 < K; k4 += nthreads * 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p.x + k4);
-      ss = sumsq4(ss, v);
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += red[i];
-    rstd = rsqrtf(t / (float)K + p.eps);
-  }
-  for (int k4 = tid * 4; k4 < nchunks * 512; k4 += nthreads * 4) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (k4 < K) {
-      v = *reinterpret_cast<const f32x4*>(p.x + k4);
-      if (NORM) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(p.norm_w + k4);
-        v.x = g.x * (v.x * rstd); v.y = g.y * (v.y * rstd); v.z = g.z * (v.z * rstd); v.w = g.w * (v.w * rstd);
-      }
-    }
+// bf16: 16-byte loads of 8 weights, 512-element chunks, x staged as [chunk][half][lane] float4.
+struct FmtBf16 {
+  static constexpr int kShift = 9;
+  struct Row { const uint16_t* w; };
+  typedef u32x4 Load;
+  struct X { f32x4 a, b; };
+  typedef float Acc;
+  __device__ __forceinline__ explicit FmtBf16(const GemvParams&) {}
+  static __device__ __forceinline__ void stage(char* smem, int k4, const f32x4 v) {
     const int chunk = k4 >> 9, within = k4 & 511;
-    xs4[chunk * 128 + ((within >> 2) & 1) * 64 + (within >> 3)] = v;
+    reinterpret_cast<f32x4*>(smem)[chunk * 128 + ((within >> 2) & 1) * 64 + (within >> 3)] = v;
   }
-  __syncthreads();
+  __device__ __forceinline__ Row row(const GemvParams& p, int row, int lane) const { return {p.w + (size_t)row * p.ldw + lane * 8}; }
+  __device__ __forceinline__ Load load(const Row& r, int c, int, bool ok) const {
+    Load wv = {0u, 0u, 0u, 0u};
+    if (ok) wv = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(r.w + (c << 9)));
+    return wv;
+  }
+  static __device__ __forceinline__ X x(const char* smem, int c, int lane) {
+    const f32x4* xs4 = reinterpret_cast<const f32x4*>(smem);
+    return {xs4[c * 128 + lane], xs4[c * 128 + 64 + lane]};
+  }
+  static __device__ __forceinline__ void dot(const Load wv, const X& x, Acc& acc) { acc = dot8(wv, x.a, x.b, acc); }
+  static __device__ __forceinline__ float sum(const Acc& acc) { return acc; }
+  static __device__ __forceinline__ float post(float s, const Row&) { return s; }
+};
 
-  for (int task = blockIdx.x * nw + wave; task < p.tasks; task += gridDim.x * nw) {
-    const uint16_t* wrow[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      int row = task_row<ROWS, EPI>(task, r);
-      if (row >= p.n) row = 0;
-      wrow[r] = p.w + (size_t)row * p.ldw + lane * 8;
-    }
-    float acc[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
-    for (int c = 0; c < nchunks; c += UNR) {
-      u32x4 wv[UNR][ROWS];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const bool ok = c + u < nchunks && ((c + u) << 9) + lane * 8 < K;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          wv[u][r] = (u32x4){0u, 0u, 0u, 0u};
-          if (ok) wv[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + ((c + u) << 9)));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        if (c + u < nchunks) {
-          const f32x4 xa = xs4[(c + u) * 128 + lane], xb = xs4[(c + u) * 128 + 64 + lane];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) acc[r] = dot8(wv[u][r], xa, xb, acc[r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = wave_sum(acc[r]);
-    gemv_epilogue<ROWS, EPI>(p, task, lane, acc, epoch);
-  }
-  if (EPI == kEpiResidTp) {
-    // (no counter bump: the launch's epoch is counted by the host, TpParams::idx - a later collective of the step bumps the counter)
-    for (int task = blockIdx.x * nw + wave; task < p.tasks; task += gridDim.x * nw) tp_take_task<ROWS>(p, epoch, task, lane);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K-split form for SHARD-sized projections (a rank of TP = 4 / 8: qkv is 896 x 5120 at TP = 8 - 448 row groups for 256 CUs).  A wave
-// that walks the whole K alone is a chain of K / 1024 dependent HBM round trips, and with one or two such waves per CU nothing
-// hides them: the launch sits at 9.6 us for 9 MB (profiles/r4_tp8_shard_kernel_trace.txt) where 3.3 us + bytes / 6.7 TB/s says 4.7.
-// Here p.ks waves share a row group: wave j of the group takes the chunk pairs j, j + ks, ... (all of its loads in flight at once when
-// ks = chunks / 2), the partial sums meet in LDS and wave 0 of the group adds them in wave order (fixed -> reproducible; NOT the
-// bits of the whole-K kernel, which stays the one every TP = 1 shape runs) and applies the epilogue.  Same x staging / fused RMSNorm.
-// ------------------------------------------------------------------------------------------------
-template <int EPI, bool NORM>
-__global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvParams p) {
-  constexpr int ROWS = 2, UNR = 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  f32x4* xs4 = reinterpret_cast<f32x4*>(smem);            // permuted x: [chunk][half][lane] float4
-  float* red = reinterpret_cast<float*>(smem) + (size_t)((p.k + 511) / 512) * 512;
-  float* part = red + 16;                                 // [nw][ROWS] partial sums of the K-slices
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nthreads = blockDim.x, nw = nthreads >> 6;
-  const int K = p.k;
-  const int nchunks = (K + 511) >> 9;
-
-  float rstd = 1.f;
-  if (NORM) {
-    float ss = 0.f;
-    for (int k4 = tid * 4; k4 < K; k4 += nthreads * 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p.x + k4);
-      ss = sumsq4(ss, v);
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += red[i];
-    rstd = rsqrtf(t / (float)K + p.eps);
-  }
-  for (int k4 = tid * 4; k4 < nchunks * 512; k4 += nthreads * 4) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (k4 < K) {
-      v = *reinterpret_cast<const f32x4*>(p.x + k4);
-      if (NORM) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(p.norm_w + k4);
-        v.x = g.x * (v.x * rstd); v.y = g.y * (v.y * rstd); v.z = g.z * (v.z * rstd); v.w = g.w * (v.w * rstd);
-      }
-    }
-    const int chunk = k4 >> 9, within = k4 & 511;
-    xs4[chunk * 128 + ((within >> 2) & 1) * 64 + (within >> 3)] = v;
-  }
-  __syncthreads();
-
-  const int ks = p.ks, ngroups = nw / ks, grp = wave / ks, j = wave - grp * ks;
-  for (int t0 = blockIdx.x * ngroups; t0 < p.tasks; t0 += gridDim.x * ngroups) {      // (uniform trip count: barriers inside)
-    const int task = t0 + grp;
-    const bool valid = grp < ngroups && task < p.tasks;
-    float acc[ROWS] = {0.f, 0.f};
-    if (valid) {
-      const uint16_t* wrow[ROWS];
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        int row = task_row<ROWS, EPI>(task, r);
-        if (row >= p.n) row = 0;
-        wrow[r] = p.w + (size_t)row * p.ldw + lane * 8;
-      }
-      for (int c = j * UNR; c < nchunks; c += ks * UNR) {
-        u32x4 wv[UNR][ROWS];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-          const bool ok = c + u < nchunks && ((c + u) << 9) + lane * 8 < K;
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) {
-            wv[u][r] = (u32x4){0u, 0u, 0u, 0u};
-            if (ok) wv[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + ((c + u) << 9)));
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-          if (c + u < nchunks) {
-            const f32x4 xa = xs4[(c + u) * 128 + lane], xb = xs4[(c + u) * 128 + 64 + lane];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) acc[r] = dot8(wv[u][r], xa, xb, acc[r]);
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) acc[r] = wave_sum(acc[r]);
-      if (lane == 0) { part[wave * ROWS] = acc[0]; part[wave * ROWS + 1] = acc[1]; }
-    }
-    __syncthreads();
-    if (valid && j == 0) {
-      float tot[ROWS];
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        tot[r] = part[wave * ROWS + r];
-        for (int i = 1; i < ks; ++i) tot[r] += part[(wave + i) * ROWS + r];          // wave order: fixed
-      }
-      gemv_epilogue<ROWS, EPI>(p, task, lane, tot);
-    }
-    __syncthreads();
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp8 weights (OCP e4m3fn, CDNA4 v_cvt_pk_f32_fp8): the same geometry with 16 weights per 16-byte load, so a
-// chunk is 1024 elements and x is staged as [chunk][quarter][lane] float4.  Each row carries a power-of-two
-// scale, w = scale[row] * float(q): the dequantised weight is exactly representable in bf16, i.e. the fp8 copy
-// is a lossless encoding of the bf16 matrix the prefill GEMM streams.  Halves the decode weight traffic.
-// ------------------------------------------------------------------------------------------------
+// 8-bit weights, fp8 (OCP e4m3fn, CDNA4 v_cvt_pk_f32_fp8) or int8: 16 weights per 16-byte load, so a chunk is 1024 elements and x is
+// staged as [chunk][quarter][lane] float4.  Each row carries a power-of-two scale, w = scale[row] * float(q): the dequantised weight is
+// exactly representable in bf16, i.e. the 8-bit copy is a lossless encoding of the bf16 matrix the prefill GEMM streams.  Halves the
+// decode weight traffic.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float dot16_fp8(const u32x4 wv, const f32x4 x0, const f32x4 x1, const f32x4 x2, const f32x4 x3,
@@ -345,99 +193,44 @@ __device__ __forceinline__ float dot16_i8(const u32x4 wv, const f32x4 x0, const 
   return acc;
 }
 
-template <int ROWS, int UNR, int EPI, bool NORM, bool I8 = false>
-__global__ __launch_bounds__(1024) void gemv8_ldsx_kernel(GemvParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  f32x4* xs4 = reinterpret_cast<f32x4*>(smem);            // permuted x: [chunk][quarter][lane] float4
-  const int K = p.k;
-  const int nchunks = (K + 1023) >> 10;
-  float* red = reinterpret_cast<float*>(smem) + (size_t)nchunks * 1024;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nthreads = blockDim.x, nw = nthreads >> 6;
-  uint32_t epoch = 0;
-  if (EPI == kEpiResidTp) epoch = tp_epoch(p.tp);
-
-  float rstd = 1.f;
-  if (NORM) {
-    float ss = 0.f;
-    for (int k4 = tid * 4; k4 < K; k4 += nthreads * 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(p.x + k4);
-      ss = sumsq4(ss, v);
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += red[i];
-    rstd = rsqrtf(t / (float)K + p.eps);
-  }
-  for (int k4 = tid * 4; k4 < nchunks * 1024; k4 += nthreads * 4) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (k4 < K) {
-      v = *reinterpret_cast<const f32x4*>(p.x + k4);
-      if (NORM) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(p.norm_w + k4);
-        v.x = g.x * (v.x * rstd); v.y = g.y * (v.y * rstd); v.z = g.z * (v.z * rstd); v.w = g.w * (v.w * rstd);
-      }
-    }
+template <bool I8>
+struct FmtW8 {
+  static constexpr int kShift = 10;
+  struct Row { const uint8_t* w; float scale; };
+  typedef u32x4 Load;
+  struct X { f32x4 x0, x1, x2, x3; };
+  typedef float Acc;
+  __device__ __forceinline__ explicit FmtW8(const GemvParams&) {}
+  static __device__ __forceinline__ void stage(char* smem, int k4, const f32x4 v) {
     const int chunk = k4 >> 10, within = k4 & 1023;
-    xs4[chunk * 256 + ((within >> 2) & 3) * 64 + (within >> 4)] = v;
+    reinterpret_cast<f32x4*>(smem)[chunk * 256 + ((within >> 2) & 3) * 64 + (within >> 4)] = v;
   }
-  __syncthreads();
+  // (the scale is loaded here, before the stream loop: its latency hides under the weight loads)
+  __device__ __forceinline__ Row row(const GemvParams& p, int row, int lane) const {
+    return {p.w8 + (size_t)row * p.ldw8 + lane * 16, p.w8_scale[row]};
+  }
+  __device__ __forceinline__ Load load(const Row& r, int c, int, bool ok) const {
+    Load wv = {0u, 0u, 0u, 0u};
+    if (ok) wv = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(r.w + (c << 10)));
+    return wv;
+  }
+  static __device__ __forceinline__ X x(const char* smem, int c, int lane) {
+    const f32x4* xb = reinterpret_cast<const f32x4*>(smem) + c * 256 + lane;
+    return {xb[0], xb[64], xb[128], xb[192]};
+  }
+  static __device__ __forceinline__ void dot(const Load wv, const X& x, Acc& acc) {
+    acc = I8 ? dot16_i8(wv, x.x0, x.x1, x.x2, x.x3, acc) : dot16_fp8(wv, x.x0, x.x1, x.x2, x.x3, acc);
+  }
+  static __device__ __forceinline__ float sum(const Acc& acc) { return acc; }
+  static __device__ __forceinline__ float post(float s, const Row& r) { return s * r.scale; }      // power-of-two scale: exact
+};
 
-  for (int task = blockIdx.x * nw + wave; task < p.tasks; task += gridDim.x * nw) {
-    const uint8_t* wrow[ROWS];
-    float scale[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      int row = task_row<ROWS, EPI>(task, r);
-      if (row >= p.n) row = 0;
-      wrow[r] = p.w8 + (size_t)row * p.ldw8 + lane * 16;
-      scale[r] = p.w8_scale[row];
-    }
-    float acc[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
-    for (int c = 0; c < nchunks; c += UNR) {
-      u32x4 wv[UNR][ROWS];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const bool ok = c + u < nchunks && ((c + u) << 10) + lane * 16 < K;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          wv[u][r] = (u32x4){0u, 0u, 0u, 0u};
-          if (ok) wv[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wrow[r] + ((c + u) << 10)));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        if (c + u < nchunks) {
-          const f32x4* xb = xs4 + (c + u) * 256 + lane;
-          const f32x4 x0 = xb[0], x1 = xb[64], x2 = xb[128], x3 = xb[192];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) acc[r] = I8 ? dot16_i8(wv[u][r], x0, x1, x2, x3, acc[r]) : dot16_fp8(wv[u][r], x0, x1, x2, x3, acc[r]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = wave_sum(acc[r]) * scale[r];     // power-of-two scale: exact
-    gemv_epilogue<ROWS, EPI>(p, task, lane, acc, epoch);
-  }
-  if (EPI == kEpiResidTp) {
-    // (no counter bump: the launch's epoch is counted by the host, TpParams::idx - a later collective of the step bumps the counter)
-    for (int task = blockIdx.x * nw + wave; task < p.tasks; task += gridDim.x * nw) tp_take_task<ROWS>(p, epoch, task, lane);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// 4-bit weights (GPTQ-Int4 checkpoints: ChatTS-14B-GPTQ-Int4, NetManAIOps/ChatTS README.md:52,262-263).  Same geometry as the
-// fp8 kernel - a lane's load is 8 bytes = 16 codes, a chunk is 1024 elements, x staged as [chunk][quarter][lane] float4 -
-// with a (scale, scale * zero) pair per group of `w4_group` (a multiple of 16) weights.  The engine's weights are DEFINED as
-// bf16_rne(scale * (q - zero)) (chatts_amd/gptq.py: the prefill GEMM streams that bf16 matrix), so the kernel rebuilds exactly
-// that value: q * scale - scale * zero is exact in float32 (fp16 scale x 5-bit integer), one v_cvt_pk_bf16_f32 per pair rounds
-// it, and the widened result meets x in the same exact-product float32 FMA as everywhere else.  ~5 VALU ops per weight at
-// 0.5 B per weight: the VALU and HBM are about equally loaded.
-// ------------------------------------------------------------------------------------------------
+// 4-bit weights (GPTQ-Int4 checkpoints: ChatTS-14B-GPTQ-Int4, NetManAIOps/ChatTS README.md:52,262-263).  A lane's load is 8 bytes = 16
+// codes, a chunk is 1024 elements, with a (scale, scale * zero) pair per group of `w4_group` (a multiple of 16) weights.  The engine's
+// weights are DEFINED as bf16_rne(scale * (q - zero)) (chatts_amd/gptq.py: the prefill GEMM streams that bf16 matrix), so the kernel
+// rebuilds exactly that value: q * scale - scale * zero is exact in float32 (fp16 scale x 5-bit integer), one v_cvt_pk_bf16_f32 per
+// pair rounds it, and the widened result meets x in an exact-product float32 accumulate.  ~5 VALU ops per weight at 0.5 B per weight:
+// the VALU and HBM are about equally loaded.
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 // 16 codes (two dwords) of one row against 16 x values held as packed bf16 pairs (hi and lo planes of the float32 x):
@@ -469,18 +262,57 @@ __device__ __forceinline__ void dot16_int4(const u32x2 wv, const float sc, const
   eight(wv.y, xh1, xl1);
 }
 
-template <int ROWS, int UNR, int EPI, bool NORM>
-__global__ __launch_bounds__(1024) void gemv4_ldsx_kernel(GemvParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+struct FmtInt4 {
+  static constexpr int kShift = 10;
+  struct Row { const uint8_t* w; const float2* sz; };
+  struct Load { u32x2 w; float2 sz; };
+  struct X { u32x4 h0, h1, l0, l1; };
+  struct Acc { float h, l; };
+  int ngroups, gshift;                                     // group sizes are powers of two (checked by the launcher)
+  __device__ __forceinline__ explicit FmtInt4(const GemvParams& p) : ngroups(p.k / p.w4_group), gshift(31 - __builtin_clz(p.w4_group)) {}
   // x as packed bf16 pairs: [chunk][part][lane] 16-byte entries; part 0 / 1 = hi pairs 0-3 / 4-7 of the lane's 16 elements,
   // part 2 / 3 = the lo pairs (x = hi + lo to 2^-17: the bf16x2 split)
-  u32x4* xs4 = reinterpret_cast<u32x4*>(smem);
-  const int K = p.k;
-  const int nchunks = (K + 1023) >> 10;
-  float* red = reinterpret_cast<float*>(smem) + (size_t)nchunks * 1024;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nthreads = blockDim.x, nw = nthreads >> 6;
+  static __device__ __forceinline__ void stage(char* smem, int k4, const f32x4 v) {
+    uint32_t* xs1 = reinterpret_cast<uint32_t*>(smem);
+    uint16_t h[4], l[4];
+    split_bf16x2(v.x, h[0], l[0]); split_bf16x2(v.y, h[1], l[1]); split_bf16x2(v.z, h[2], l[2]); split_bf16x2(v.w, h[3], l[3]);
+    const int chunk = k4 >> 10, within = k4 & 1023, ln = within >> 4, pair = (within & 15) >> 1;      // pair in {0, 2, 4, 6}
+    const int base = ((chunk * 4 + (pair >> 2)) * 64 + ln) * 4 + (pair & 3);                            // dword index of the hi pair
+    xs1[base] = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+    xs1[base + 1] = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+    xs1[base + 2 * 64 * 4] = (uint32_t)l[0] | ((uint32_t)l[1] << 16);
+    xs1[base + 2 * 64 * 4 + 1] = (uint32_t)l[2] | ((uint32_t)l[3] << 16);
+  }
+  __device__ __forceinline__ Row row(const GemvParams& p, int row, int lane) const {
+    return {p.w4 + (size_t)row * p.ldw4 + lane * 8, reinterpret_cast<const float2*>(p.w4_sz) + (size_t)row * ngroups};
+  }
+  __device__ __forceinline__ Load load(const Row& r, int c, int k0, bool ok) const {
+    Load wv = {(u32x2){0u, 0u}, make_float2(0.f, 0.f)};
+    if (ok) {
+      wv.w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(r.w + (c << 9)));
+      wv.sz = r.sz[k0 >> gshift];
+    }
+    return wv;
+  }
+  static __device__ __forceinline__ X x(const char* smem, int c, int lane) {
+    const u32x4* xb = reinterpret_cast<const u32x4*>(smem) + c * 256 + lane;
+    return {xb[0], xb[64], xb[128], xb[192]};
+  }
+  static __device__ __forceinline__ void dot(const Load& wv, const X& x, Acc& acc) {
+    dot16_int4(wv.w, wv.sz.x, -wv.sz.y, x.h0, x.h1, x.l0, x.l1, acc.h, acc.l);
+  }
+  static __device__ __forceinline__ float sum(const Acc& acc) { return acc.h + acc.l; }
+  static __device__ __forceinline__ float post(float s, const Row&) { return s; }
+};
 
+// ---- the prologue: rstd of the fused RMSNorm and x, zero-padded to whole chunks, into LDS ------------------------------------------------
+// -> red (behind the staged x: nw floats; the K-split kernel keeps its partial sums at red + 16).  The order of the sum of squares -
+// per thread at stride blockDim.x * 4, wave_sum, the waves in wave order - is part of the result's bits: rstd depends on the wave count.
+template <class F, bool NORM>
+__device__ __forceinline__ float* gemv_stage_x(const GemvParams& p, char* smem, int nchunks, int tid, int nthreads) {
+  float* red = reinterpret_cast<float*>(smem) + ((size_t)nchunks << F::kShift);
+  const int lane = tid & 63, wave = tid >> 6, nw = nthreads >> 6;
+  const int K = p.k;
   float rstd = 1.f;
   if (NORM) {
     float ss = 0.f;
@@ -495,8 +327,7 @@ __global__ __launch_bounds__(1024) void gemv4_ldsx_kernel(GemvParams p) {
     for (int i = 0; i < nw; ++i) t += red[i];
     rstd = rsqrtf(t / (float)K + p.eps);
   }
-  uint32_t* xs1 = reinterpret_cast<uint32_t*>(smem);
-  for (int k4 = tid * 4; k4 < nchunks * 1024; k4 += nthreads * 4) {
+  for (int k4 = tid * 4; k4 < (nchunks << F::kShift); k4 += nthreads * 4) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (k4 < K) {
       v = *reinterpret_cast<const f32x4*>(p.x + k4);
@@ -505,111 +336,136 @@ __global__ __launch_bounds__(1024) void gemv4_ldsx_kernel(GemvParams p) {
         v.x = g.x * (v.x * rstd); v.y = g.y * (v.y * rstd); v.z = g.z * (v.z * rstd); v.w = g.w * (v.w * rstd);
       }
     }
-    uint16_t h[4], l[4];
-    split_bf16x2(v.x, h[0], l[0]); split_bf16x2(v.y, h[1], l[1]); split_bf16x2(v.z, h[2], l[2]); split_bf16x2(v.w, h[3], l[3]);
-    const int chunk = k4 >> 10, within = k4 & 1023, ln = within >> 4, pair = (within & 15) >> 1;      // pair in {0, 2, 4, 6}
-    const int base = ((chunk * 4 + (pair >> 2)) * 64 + ln) * 4 + (pair & 3);                            // dword index of the hi pair
-    xs1[base] = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-    xs1[base + 1] = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-    xs1[base + 2 * 64 * 4] = (uint32_t)l[0] | ((uint32_t)l[1] << 16);
-    xs1[base + 2 * 64 * 4 + 1] = (uint32_t)l[2] | ((uint32_t)l[3] << 16);
+    F::stage(smem, k4, v);
   }
   __syncthreads();
+  return red;
+}
 
-  const int ngroups = K / p.w4_group;
-  const int gshift = 31 - __builtin_clz(p.w4_group);        // group sizes are powers of two (checked by the launcher)
+// ---- the stream loop: the ROWS rows of a task against the chunks c0, c0 + cstep, ... (UNR of them per step) -> per-row wave sums ------------
+// ROWS x UNR loads are issued before the first of them is used.  Out-of-range loads leave zero registers, out-of-range rows read row 0
+// (their sums are never stored); a row's chunks are added in ascending order whatever ROWS and UNR are.
+template <class F, int ROWS, int UNR, int EPI>
+__device__ __forceinline__ void gemv_stream(const F& f, const GemvParams& p, const char* smem, int task, int lane, int nchunks, int c0,
+                                            int cstep, float (&acc)[ROWS]) {
+  const int K = p.k;
+  typename F::Row rw[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) {
+    int row = task_row<ROWS, EPI>(task, r);
+    if (row >= p.n) row = 0;
+    rw[r] = f.row(p, row, lane);
+  }
+  typename F::Acc part[ROWS] = {};
+  for (int c = c0; c < nchunks; c += cstep) {
+    typename F::Load wv[UNR][ROWS];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int k0 = ((c + u) << F::kShift) + lane * ((1 << F::kShift) / 64);
+      const bool ok = c + u < nchunks && k0 < K;
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) wv[u][r] = f.load(rw[r], c + u, k0, ok);
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      if (c + u < nchunks) {
+        const typename F::X x = F::x(smem, c + u, lane);
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) F::dot(wv[u][r], x, part[r]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) acc[r] = F::post(wave_sum(F::sum(part[r])), rw[r]);
+}
+
+// ---- the whole-K task loop: blockDim = 64 * NW (any 1..16 waves share one staged copy of x), one wave per task, then the exchange tail ---------
+template <class F, int ROWS, int UNR, int EPI, bool NORM>
+__device__ __forceinline__ void gemv_whole_k(const GemvParams& p, const int nthreads) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nw = nthreads >> 6;
+  const int nchunks = (p.k + (1 << F::kShift) - 1) >> F::kShift;
+  uint32_t epoch = 0;
+  if (EPI == kEpiResidTp) epoch = tp_epoch(p.tp);
+  gemv_stage_x<F, NORM>(p, smem, nchunks, tid, nthreads);
+  const F f(p);
   for (int task = blockIdx.x * nw + wave; task < p.tasks; task += gridDim.x * nw) {
-    const uint8_t* wrow[ROWS];
-    const float2* szrow[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      int row = task_row<ROWS, EPI>(task, r);
-      if (row >= p.n) row = 0;
-      wrow[r] = p.w4 + (size_t)row * p.ldw4 + lane * 8;
-      szrow[r] = reinterpret_cast<const float2*>(p.w4_sz) + (size_t)row * ngroups;
-    }
-    float acc_h[ROWS], acc_l[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) { acc_h[r] = 0.f; acc_l[r] = 0.f; }
-    for (int c = 0; c < nchunks; c += UNR) {
-      u32x2 wv[UNR][ROWS];
-      float2 sz[UNR][ROWS];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const int k0 = ((c + u) << 10) + lane * 16;
-        const bool ok = c + u < nchunks && k0 < K;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          wv[u][r] = (u32x2){0u, 0u};
-          sz[u][r] = make_float2(0.f, 0.f);
-          if (ok) {
-            wv[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wrow[r] + ((c + u) << 9)));
-            sz[u][r] = szrow[r][k0 >> gshift];
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        if (c + u < nchunks) {
-          const u32x4* xb = xs4 + (c + u) * 256 + lane;
-          const u32x4 xh0 = xb[0], xh1 = xb[64], xl0 = xb[128], xl1 = xb[192];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) dot16_int4(wv[u][r], sz[u][r].x, -sz[u][r].y, xh0, xh1, xl0, xl1, acc_h[r], acc_l[r]);
-        }
-      }
-    }
     float acc[ROWS];
+    gemv_stream<F, ROWS, UNR, EPI>(f, p, smem, task, lane, nchunks, 0, UNR, acc);
+    gemv_epilogue<ROWS, EPI>(p, task, lane, acc, epoch);
+  }
+  if (EPI == kEpiResidTp) {
+    // (no counter bump: the launch's epoch is counted by the host, TpParams::idx - a later collective of the step bumps the counter)
+    for (int task = blockIdx.x * nw + wave; task < p.tasks; task += gridDim.x * nw) tp_take_task<ROWS>(p, epoch, task, lane);
+  }
+}
+
+// The entry points: the names that kernel traces, bench.py's roofline label and DESIGN.md use.  (blockDim.x is read here, once: only in
+// a __global__ function does the compiler know the workgroups to be uniform and fold the read to one scalar load.)
+template <int ROWS, int UNR, int EPI, bool NORM>
+__global__ __launch_bounds__(1024) void gemv_ldsx_kernel(GemvParams p) { gemv_whole_k<FmtBf16, ROWS, UNR, EPI, NORM>(p, blockDim.x); }
+
+template <int ROWS, int UNR, int EPI, bool NORM, bool I8 = false>
+__global__ __launch_bounds__(1024) void gemv8_ldsx_kernel(GemvParams p) { gemv_whole_k<FmtW8<I8>, ROWS, UNR, EPI, NORM>(p, blockDim.x); }
+
+template <int ROWS, int UNR, int EPI, bool NORM>
+__global__ __launch_bounds__(1024) void gemv4_ldsx_kernel(GemvParams p) { gemv_whole_k<FmtInt4, ROWS, UNR, EPI, NORM>(p, blockDim.x); }
+
+// ------------------------------------------------------------------------------------------------
+// K-split form for SHARD-sized projections (a rank of TP = 4 / 8: qkv is 896 x 5120 at TP = 8 - 448 row groups for 256 CUs).  A wave
+// that walks the whole K alone is a chain of K / 1024 dependent HBM round trips, and with one or two such waves per CU nothing
+// hides them: the launch sits at 9.6 us for 9 MB (profiles/r4_tp8_shard_kernel_trace.txt) where 3.3 us + bytes / 6.7 TB/s says 4.7.
+// Here p.ks waves share a row group: wave j of the group takes the chunk pairs j, j + ks, ... (all of its loads in flight at once when
+// ks = chunks / 2), the partial sums meet in LDS and wave 0 of the group adds them in wave order (fixed -> reproducible; NOT the
+// bits of the whole-K kernel, which stays the one every TP = 1 shape runs) and applies the epilogue.  Same prologue, same stream loop.
+// ------------------------------------------------------------------------------------------------
+template <int EPI, bool NORM>
+__global__ __launch_bounds__(1024) void gemv_ksplit_kernel(GemvParams p) {
+  constexpr int ROWS = 2, UNR = 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nthreads = blockDim.x, nw = nthreads >> 6;
+  const int nchunks = (p.k + 511) >> 9;
+  float* part = gemv_stage_x<FmtBf16, NORM>(p, smem, nchunks, tid, nthreads) + 16;      // [nw][ROWS] partial sums of the K-slices
+  const FmtBf16 f(p);
+
+  const int ks = p.ks, ngroups = nw / ks, grp = wave / ks, j = wave - grp * ks;
+  for (int t0 = blockIdx.x * ngroups; t0 < p.tasks; t0 += gridDim.x * ngroups) {      // (uniform trip count: barriers inside)
+    const int task = t0 + grp;
+    const bool valid = grp < ngroups && task < p.tasks;
+    float acc[ROWS] = {0.f, 0.f};
+    if (valid) {
+      gemv_stream<FmtBf16, ROWS, UNR, EPI>(f, p, smem, task, lane, nchunks, j * UNR, ks * UNR, acc);
+      if (lane == 0) { part[wave * ROWS] = acc[0]; part[wave * ROWS + 1] = acc[1]; }
+    }
+    __syncthreads();
+    if (valid && j == 0) {
+      float tot[ROWS];
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = wave_sum(acc_h[r] + acc_l[r]);
-    gemv_epilogue<ROWS, EPI>(p, task, lane, acc);
+      for (int r = 0; r < ROWS; ++r) {
+        tot[r] = part[wave * ROWS + r];
+        for (int i = 1; i < ks; ++i) tot[r] += part[(wave + i) * ROWS + r];          // wave order: fixed
+      }
+      gemv_epilogue<ROWS, EPI>(p, task, lane, tot);
+    }
+    __syncthreads();
   }
 }
 
-// ---- dispatch ------------------------------------------------------------------------------------
-template <int ROWS, int UNR, int EPI>
-static void launch_ldsx_norm(const GemvParams& p, bool norm, int blocks, int threads, size_t lds, hipStream_t s) {
-  if (norm) hipLaunchKernelGGL((gemv_ldsx_kernel<ROWS, UNR, EPI, true>), dim3(blocks), dim3(threads), lds, s, p);
-  else hipLaunchKernelGGL((gemv_ldsx_kernel<ROWS, UNR, EPI, false>), dim3(blocks), dim3(threads), lds, s, p);
-}
-template <int ROWS, int UNR>
-static void launch_ldsx(const GemvParams& p, int epi, bool norm, int blocks, int threads, size_t lds, hipStream_t s) {
-  switch (epi) {
-    case CHATTS_EPI_RESID: launch_ldsx_norm<ROWS, UNR, CHATTS_EPI_RESID>(p, norm, blocks, threads, lds, s); break;
-    case kEpiResidTp: hipLaunchKernelGGL((gemv_ldsx_kernel<ROWS, UNR, kEpiResidTp, false>), dim3(blocks), dim3(threads), lds, s, p); break;
-    case CHATTS_EPI_SWIGLU: launch_ldsx_norm<ROWS, UNR, CHATTS_EPI_SWIGLU>(p, norm, blocks, threads, lds, s); break;
-    default: launch_ldsx_norm<ROWS, UNR, CHATTS_EPI_NONE>(p, norm, blocks, threads, lds, s); break;
-  }
-}
+// ---- launch geometry -------------------------------------------------------------------------------------------------------------
+enum GemvFormat { kBf16 = 0, kW8 = 1, kInt4 = 2 };
 
-template <int EPI>
-static void launch4_norm(const GemvParams& p, bool norm, int blocks, int threads, size_t lds, hipStream_t s) {
-  if (norm) hipLaunchKernelGGL((gemv4_ldsx_kernel<2, 4, EPI, true>), dim3(blocks), dim3(threads), lds, s, p);
-  else hipLaunchKernelGGL((gemv4_ldsx_kernel<2, 4, EPI, false>), dim3(blocks), dim3(threads), lds, s, p);
-}
-
-template <int ROWS, int UNR, int EPI>
-static void launch8_ru(const GemvParams& p, bool norm, int blocks, int threads, size_t lds, hipStream_t s) {
-  if (p.w8_format == CHATTS_W8_INT8) {
-    if (norm) hipLaunchKernelGGL((gemv8_ldsx_kernel<ROWS, UNR, EPI, true, true>), dim3(blocks), dim3(threads), lds, s, p);
-    else hipLaunchKernelGGL((gemv8_ldsx_kernel<ROWS, UNR, EPI, false, true>), dim3(blocks), dim3(threads), lds, s, p);
-    return;
-  }
-  if (norm) hipLaunchKernelGGL((gemv8_ldsx_kernel<ROWS, UNR, EPI, true>), dim3(blocks), dim3(threads), lds, s, p);
-  else hipLaunchKernelGGL((gemv8_ldsx_kernel<ROWS, UNR, EPI, false>), dim3(blocks), dim3(threads), lds, s, p);
-}
-template <int EPI>
-static void launch8_norm(const GemvParams& p, bool norm, int rows, int unr, int blocks, int threads, size_t lds, hipStream_t s) {
-  if (rows == 4 && unr == 2) launch8_ru<4, 2, EPI>(p, norm, blocks, threads, lds, s);
-  else if (rows == 4) launch8_ru<4, 1, EPI>(p, norm, blocks, threads, lds, s);
-  else if (unr == 4) launch8_ru<2, 4, EPI>(p, norm, blocks, threads, lds, s);
-  else launch8_ru<2, 2, EPI>(p, norm, blocks, threads, lds, s);
-}
-
-// Waves per workgroup (and workgroups per CU, 0 = whatever fits) of the bf16 GEMV for a shape: the sweep results of
-// tools/gemv_sweep.py.  Also read by decode_mega.hip, whose fused RMSNorm reproduces this kernel's summation order.
-void gemv_default_geometry(int n, int k, int epilogue, int cus, int* nw_out, int* occ_out) {
+// row-group tasks of a projection: `rows` rows each, or rows / 2 gate / up pairs
+static int gemv_tasks(int n, int epilogue, int rows) {
   const int swiglu = epilogue == CHATTS_EPI_SWIGLU;
-  const int units = swiglu ? n / 2 : n;
+  const int units = swiglu ? n / 2 : n, upt = swiglu ? rows / 2 : rows;
+  return (units + upt - 1) / upt;
+}
+
+// Waves per workgroup (and workgroups per CU, 0 = whatever fits) of the GEMV for a shape: the sweep results of tools/gemv_sweep.py.
+static void gemv_default_geometry(int n, int k, int epilogue, int cus, int* nw_out, int* occ_out) {
+  const int units = epilogue == CHATTS_EPI_SWIGLU ? n / 2 : n;
   int nw_auto, occ_auto = 0;
   if (k > 8192) nw_auto = 16;                       // down_proj: 55 KB of x per workgroup -> amortise over 16 waves
   else if (units >= 65536) { nw_auto = 4; occ_auto = 2; }   // lm_head
@@ -619,7 +475,7 @@ void gemv_default_geometry(int n, int k, int epilogue, int cus, int* nw_out, int
   // Balanced layout (profiles/r2_gemv_sweep_balanced.txt): when the CUs divide the row-group tasks, one workgroup per CU whose
   // wave count divides the tasks per CU gives every wave the same number of tasks (no ragged last round): o_proj 11.5 ->
   // 11.2 us, gate_up 44.5 -> 44.1, down_proj 24.9 -> 24.5; lm_head (297 tasks per CU) keeps the 2-workgroup layout.
-  const int tasks_r2 = (units + (swiglu ? 0 : 1)) / (swiglu ? 1 : 2);
+  const int tasks_r2 = gemv_tasks(n, epilogue, 2);
   int balanced_nw = 0;
   if (units < 65536 && tasks_r2 % cus == 0) {
     const int per_cu = tasks_r2 / cus;
@@ -635,7 +491,7 @@ void gemv_default_geometry(int n, int k, int epilogue, int cus, int* nw_out, int
 // shapes take which kernel (tests/test_host_logic.py: every TP = 1 projection of the supported models resolves to 1 - the K-split form
 // sums a row in another order - and the TP = 8 shard shapes to > 1).
 //   tasks = row groups (2 rows, or one gate / up pair), nchunks = K / 512, w_bytes = N K 2.
-int gemv_pick_ksplit(int tasks, int nchunks, bool norm, double w_bytes, int cus) {
+static int gemv_pick_ksplit(int tasks, int nchunks, bool norm, double w_bytes, int cus) {
   if (nchunks < 4) return 1;
   int ks = 1;
   const double per_cu = (double)tasks / cus;
@@ -656,6 +512,116 @@ int gemv_pick_ksplit(int tasks, int nchunks, bool norm, double w_bytes, int cus)
   return ks;
 }
 
+struct GemvGeometry {
+  int rows, unr;        // rows per wave, chunks in flight per row
+  int nw, occ;          // waves per workgroup, workgroups per CU
+  int tasks, blocks, threads;
+  size_t lds;           // dynamic LDS of the launch
+};
+
+// The geometry of the whole-K launch of a call.  Defaults from the sweep in tools/gemv_sweep.py (profiles/gemv_sweep_r1.log): what varies
+// with the shape is how many waves share one staged copy of x and how many workgroups a CU should hold.  Where the formats differ, the
+// line says why.
+static GemvGeometry gemv_geometry(const ChattsLinearArgs* a, GemvFormat fmt, int cus) {
+  const int swiglu = a->epilogue == CHATTS_EPI_SWIGLU;
+  const int units = swiglu ? a->n / 2 : a->n;
+  GemvGeometry g;
+  if (fmt == kInt4) {                  // the one form the 4-bit sweep kept: 2 rows x 4 chunks (8-byte loads) in flight
+    g.rows = 2; g.unr = 4;
+  } else if (fmt == kW8) {
+    // per shape (kernel trace of the fp8 bench under each geometry, profiles/r6_gemv8_geometry.txt): the vocabulary projection wants 4 rows x 2
+    // chunks in flight (778 MB: 144.8 -> 125.0 us), gate_up 4 rows x 1 (27.8 -> 26.9 us); the shorter launches keep 2 x 2 (4 rows halve
+    // their task count: o / down 11.8 -> 14.5 us, qkv 10.3 -> 13.1)
+    const int rows_auto = (units >= 65536 || (swiglu && a->n >= 16384)) ? 4 : 2, unr_auto = swiglu && a->n >= 16384 ? 1 : 2;
+    g.rows = opt_get(OPT_GEMV8_ROWS, rows_auto); g.unr = opt_get(OPT_GEMV8_UNR, unr_auto);
+    if (g.rows != 4 || a->tp_reduce) g.rows = 2;          // (the exchange-carrying form pushes 2 rows per task: tp_push_task's lane map)
+    if (g.rows == 4) g.unr = g.unr == 2 ? 2 : 1;          // instantiated: <2,2> <2,4> <4,2> <4,1>
+    else if (g.unr != 4) g.unr = 2;
+  } else {                             // 2 x 2 wins on every decode shape; instantiated: <2,2> <2,4> <4,2> <4,4>
+    g.rows = opt_get(OPT_GEMV_ROWS, 2) == 4 ? 4 : 2;
+    g.unr = opt_get(OPT_GEMV_UNR, 2) == 4 ? 4 : 2;
+  }
+  int nw_auto, occ_auto;
+  gemv_default_geometry(a->n, a->k, a->epilogue, cus, &nw_auto, &occ_auto);
+  g.nw = opt_get(OPT_GEMV_NW, nw_auto);
+  if (g.nw < 1 || g.nw > 16) g.nw = 4;
+  if (fmt == kW8) {                    // GEMV8_NW: the 8-bit sweeps vary the wave count without moving the bf16 launches
+    const int nw8 = opt_get(OPT_GEMV8_NW, g.nw);
+    if (nw8 >= 1 && nw8 <= 16) g.nw = nw8;
+  }
+  const int chunk = fmt == kBf16 ? 512 : 1024;
+  g.lds = (size_t)((a->k + chunk - 1) / chunk) * chunk * 4 + 64 * 4;
+  if (fmt == kInt4) {
+    // ~5 VALU ops per weight make this kernel ALU-latency bound: it wants every wave slot the registers allow (89 VGPRs -> 5 per
+    // SIMD = 20 per CU), i.e. two workgroups per CU, not the one of the bf16 layouts
+    g.occ = 20 / g.nw >= 1 ? 20 / g.nw : 1;
+  } else {
+    g.occ = (int)((150 * 1024) / g.lds);          // workgroups per CU that fit in LDS
+    if (g.occ > 32 / g.nw) g.occ = 32 / g.nw;     // 32 waves per CU
+    if (occ_auto && g.occ > occ_auto) g.occ = occ_auto;
+    if (g.occ < 1) g.occ = 1;
+  }
+  g.occ = opt_get(OPT_GEMV_OCC, g.occ);
+  if (fmt == kW8) g.occ = opt_get(OPT_GEMV8_OCC, g.occ);
+  g.tasks = gemv_tasks(a->n, a->epilogue, g.rows);
+  g.blocks = (g.tasks + g.nw - 1) / g.nw;
+  if (g.blocks > cus * g.occ) g.blocks = cus * g.occ;
+  if (fmt == kBf16) g.blocks = opt_get(OPT_GEMV_BLOCKS, g.blocks);      // (a test and sweep knob of the bf16 kernel: the tools that set it run bf16)
+  // several emulated ranks on ONE device (tests, tools/jobs): their exchange-carrying launches wait for each other, so all of them
+  // must be resident at once - cap the grid (results do not depend on it: a row is always summed by one wave in the same order)
+  if (a->tp_reduce) { const int cap = opt_get(OPT_TP_FUSE_BLOCKS, 0); if (cap > 0 && g.blocks > cap) g.blocks = cap; }
+  if (g.blocks < 1) g.blocks = 1;
+  g.threads = g.nw * 64;
+  // CHATTS_GEMV_LDSPAD = p (bf16 sweeps only, like GEMV_BLOCKS): declare 1/p of a CU's LDS, so that exactly p workgroups fit per CU and a
+  // grid of cus * p workgroups is necessarily spread evenly (every CU streams the same number of bytes)
+  const int pad = fmt == kBf16 ? opt_get(OPT_GEMV_LDSPAD, 0) : 0;
+  if (pad >= 1 && (size_t)(160 * 1024 / pad) / 16 * 16 > g.lds) {
+    const size_t need = g.lds;
+    g.lds = (size_t)(160 * 1024 / pad) / 16 * 16;
+    if (g.lds > 64 * 1024 && need <= 64 * 1024) g.lds = 64 * 1024;      // default dynamic-LDS cap of a launch (still 2 per CU)
+  }
+  return g;
+}
+
+// ---- dispatch: runtime (epilogue, norm) -> the instantiation of a kernel family ------------------------------------------------------
+// A family names its kernel for <EPI, NORM>; kTp says whether it has the exchange-carrying instantiation (kEpiResidTp, never with NORM).
+typedef void (*GemvKernel)(GemvParams);
+template <int ROWS, int UNR> struct KBf16 {
+  static constexpr bool kTp = true;
+  template <int EPI, bool NORM> static GemvKernel get() { return gemv_ldsx_kernel<ROWS, UNR, EPI, NORM>; }
+};
+template <int ROWS, int UNR, bool I8> struct KW8 {
+  static constexpr bool kTp = ROWS == 2;  // (tp_reduce launches 2 rows per task: gemv_geometry)
+  template <int EPI, bool NORM> static GemvKernel get() { return gemv8_ldsx_kernel<ROWS, UNR, EPI, NORM, I8>; }
+};
+struct KInt4 {
+  static constexpr bool kTp = false;      // (the launcher refuses tp_reduce with 4-bit codes)
+  template <int EPI, bool NORM> static GemvKernel get() { return gemv4_ldsx_kernel<2, 4, EPI, NORM>; }
+};
+struct KSplit {
+  static constexpr bool kTp = false;      // (the launcher keeps tp_reduce on the whole-K kernel)
+  template <int EPI, bool NORM> static GemvKernel get() { return gemv_ksplit_kernel<EPI, NORM>; }
+};
+
+template <class KF>
+static void gemv_dispatch(const GemvParams& p, int epi, bool norm, int blocks, int threads, size_t lds, hipStream_t s) {
+  GemvKernel k = norm ? KF::template get<CHATTS_EPI_NONE, true>() : KF::template get<CHATTS_EPI_NONE, false>();
+  if (epi == CHATTS_EPI_RESID) k = norm ? KF::template get<CHATTS_EPI_RESID, true>() : KF::template get<CHATTS_EPI_RESID, false>();
+  if (epi == CHATTS_EPI_SWIGLU) k = norm ? KF::template get<CHATTS_EPI_SWIGLU, true>() : KF::template get<CHATTS_EPI_SWIGLU, false>();
+  if constexpr (KF::kTp) {
+    if (epi == kEpiResidTp) k = KF::template get<kEpiResidTp, false>();
+  }
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, s, p);
+}
+
+template <bool I8>
+static void gemv_dispatch_w8(const GemvParams& p, const GemvGeometry& g, int epi, bool norm, hipStream_t s) {
+  if (g.rows == 4 && g.unr == 2) gemv_dispatch<KW8<4, 2, I8>>(p, epi, norm, g.blocks, g.threads, g.lds, s);
+  else if (g.rows == 4) gemv_dispatch<KW8<4, 1, I8>>(p, epi, norm, g.blocks, g.threads, g.lds, s);
+  else if (g.unr == 4) gemv_dispatch<KW8<2, 4, I8>>(p, epi, norm, g.blocks, g.threads, g.lds, s);
+  else gemv_dispatch<KW8<2, 2, I8>>(p, epi, norm, g.blocks, g.threads, g.lds, s);
+}
+
 int launch_gemv(const ChattsLinearArgs* a, hipStream_t s) {
   GemvParams p;
   p.tp = TpParams{};
@@ -663,6 +629,7 @@ int launch_gemv(const ChattsLinearArgs* a, hipStream_t s) {
   p.norm_w = a->norm_w; p.eps = a->norm_eps; p.n = a->n; p.k = a->k; p.ldw = a->ldw;
   p.w8 = a->w8; p.w8_scale = a->w8_scale; p.ldw8 = a->ldw8; p.w8_format = a->w8_format;
   p.w4 = a->w4; p.w4_sz = a->w4_sz; p.ldw4 = a->ldw4; p.w4_group = a->w4_group;
+  p.ks = 1;
   const bool norm = a->norm_w != nullptr;
   const int cus = device_cus();
   int epilogue = a->epilogue;
@@ -673,136 +640,46 @@ int launch_gemv(const ChattsLinearArgs* a, hipStream_t s) {
                    (long long)tp_capacity(a->tp_reduce));
     epilogue = kEpiResidTp;
   }
-  const int swiglu = a->epilogue == CHATTS_EPI_SWIGLU;
-  const int units = swiglu ? a->n / 2 : a->n;
   const int nchunks = (a->k + 511) / 512;
-  const size_t lds = (size_t)nchunks * 512 * 4 + 64 * 4;
-  CHATTS_REQUIRE(lds <= 160 * 1024, CHATTS_E_SHAPE, "gemv: K=%d too large for the LDS-resident x", a->k);
-  // Geometry from the sweep in tools/gemv_sweep.py (profiles/gemv_sweep_r1.log): 2 rows x 2 chunks in flight per lane
-  // wins on every decode shape; what varies is how many waves share one staged copy of x and how many
-  // workgroups a CU should hold.
-  int rows = opt_get(OPT_GEMV_ROWS, 2);
-  if (rows != 4) rows = 2;
-  int unr = opt_get(OPT_GEMV_UNR, 2);
-  if (unr != 4) unr = 2;
-  int nw_auto, occ_auto;
-  gemv_default_geometry(a->n, a->k, a->epilogue, cus, &nw_auto, &occ_auto);
-  int nw = opt_get(OPT_GEMV_NW, nw_auto);
-  if (nw < 1 || nw > 16) nw = 4;
-  int occ = (int)((150 * 1024) / lds);          // workgroups per CU that fit in LDS
-  const int wave_cap = 32 / nw;                  // 32 waves per CU
-  if (occ > wave_cap) occ = wave_cap;
-  if (occ_auto && occ > occ_auto) occ = occ_auto;
-  if (occ < 1) occ = 1;
-  occ = opt_get(OPT_GEMV_OCC, occ);
-  const int upt = swiglu ? rows / 2 : rows;
-  p.tasks = (units + upt - 1) / upt;
-  int blocks = (p.tasks + nw - 1) / nw;
-  if (blocks > cus * occ) blocks = cus * occ;
-  blocks = opt_get(OPT_GEMV_BLOCKS, blocks);
-  // several emulated ranks on ONE device (tests, tools/jobs): their exchange-carrying launches wait for each other, so all of them
-  // must be resident at once - cap the grid (results do not depend on it: a row is always summed by one wave in the same order)
-  if (a->tp_reduce) { const int cap = opt_get(OPT_TP_FUSE_BLOCKS, 0); if (cap > 0 && blocks > cap) blocks = cap; }
-  if (blocks < 1) blocks = 1;
-  const int threads = nw * 64;
-  // CHATTS_GEMV_LDSPAD = p: declare 1/p of a CU's LDS, so that exactly p workgroups fit per CU and a grid of
-  // cus * p workgroups is necessarily spread evenly (every CU streams the same number of bytes)
-  size_t lds_launch = lds;
-  const int pad = opt_get(OPT_GEMV_LDSPAD, 0);
-  if (pad >= 1 && (size_t)(160 * 1024 / pad) / 16 * 16 > lds) lds_launch = (size_t)(160 * 1024 / pad) / 16 * 16;
-  if (lds_launch > 64 * 1024 && lds <= 64 * 1024) lds_launch = 64 * 1024;      // default dynamic-LDS cap (still 2 per CU)
-  if (a->w4 != nullptr) {                       // 4-bit codes: 2 rows x 4 chunks of 1024 elements (8-byte loads) in flight
-    const int nchunks4 = (a->k + 1023) / 1024;
-    const size_t lds4 = (size_t)nchunks4 * 1024 * 4 + 64 * 4;
-    p.tasks = (units + (swiglu ? 1 : 2) - 1) / (swiglu ? 1 : 2);
-    int blocks4 = (p.tasks + nw - 1) / nw;
-    // ~5 VALU ops per weight make this kernel ALU-latency bound: it wants every wave slot the registers allow (89 VGPRs -> 5 per
-    // SIMD = 20 per CU), i.e. two workgroups per CU, not the one of the bf16 layouts
-    const int occ4 = opt_get(OPT_GEMV_OCC, 20 / nw >= 1 ? 20 / nw : 1);
-    if (blocks4 > cus * occ4) blocks4 = cus * occ4;
-    if (blocks4 < 1) blocks4 = 1;
-    switch (a->epilogue) {
-      case CHATTS_EPI_RESID: launch4_norm<CHATTS_EPI_RESID>(p, norm, blocks4, threads, lds4, s); break;
-      case CHATTS_EPI_SWIGLU: launch4_norm<CHATTS_EPI_SWIGLU>(p, norm, blocks4, threads, lds4, s); break;
-      default: launch4_norm<CHATTS_EPI_NONE>(p, norm, blocks4, threads, lds4, s); break;
-    }
-    CHATTS_CHECK_LAUNCH("gemv4_ldsx");
-    return CHATTS_OK;
-  }
-  if (a->w8 != nullptr) {                       // 8-bit weights: rows x chunks of 1024 elements in flight per lane (GEMV8_ROWS x GEMV8_UNR)
-    const int nchunks8 = (a->k + 1023) / 1024;
-    const size_t lds8 = (size_t)nchunks8 * 1024 * 4 + 64 * 4;
-    // per shape (kernel trace of the fp8 bench under each geometry, profiles/r6_gemv8_geometry.txt): the vocabulary projection wants 4 rows x 2
-    // chunks in flight (778 MB: 144.8 -> 125.0 us), gate_up 4 rows x 1 (27.8 -> 26.9 us); the shorter launches keep 2 x 2 (4 rows halve
-    // their task count: o / down 11.8 -> 14.5 us, qkv 10.3 -> 13.1)
-    const int rows_auto = (units >= 65536 || (swiglu && a->n >= 16384)) ? 4 : 2, unr_auto = swiglu && a->n >= 16384 ? 1 : 2;
-    int rows8 = opt_get(OPT_GEMV8_ROWS, rows_auto), unr8 = opt_get(OPT_GEMV8_UNR, unr_auto);
-    if (rows8 != 4 || a->tp_reduce) rows8 = 2;          // (the exchange-carrying form pushes 2 rows per task: tp_push_task's lane map)
-    if (rows8 == 4) unr8 = unr8 == 2 ? 2 : 1;
-    else if (unr8 != 4) unr8 = 2;
-    const int upt8 = swiglu ? rows8 / 2 : rows8;
-    p.tasks = (units + upt8 - 1) / upt8;
-    const int nw8 = opt_get(OPT_GEMV8_NW, nw);
-    int occ8 = (int)((150 * 1024) / lds8);
-    if (occ8 > 32 / nw8) occ8 = 32 / nw8;
-    if (occ_auto && occ8 > occ_auto) occ8 = occ_auto;
-    if (occ8 < 1) occ8 = 1;
-    occ8 = opt_get(OPT_GEMV8_OCC, opt_get(OPT_GEMV_OCC, occ8));
-    int blocks8 = (p.tasks + nw8 - 1) / nw8;
-    if (blocks8 > cus * occ8) blocks8 = cus * occ8;
-    if (a->tp_reduce) { const int cap = opt_get(OPT_TP_FUSE_BLOCKS, 0); if (cap > 0 && blocks8 > cap) blocks8 = cap; }
-    if (blocks8 < 1) blocks8 = 1;
-    const int threads8 = (nw8 >= 1 && nw8 <= 16 ? nw8 : nw) * 64;
-    if (a->tp_reduce) p.tp = tp_issue(a->tp_reduce, false);      // (after the last check that can refuse the call: one issue per launch)
-    switch (epilogue) {
-      case kEpiResidTp: launch8_norm<kEpiResidTp>(p, false, rows8, unr8, blocks8, threads8, lds8, s); break;
-      case CHATTS_EPI_RESID: launch8_norm<CHATTS_EPI_RESID>(p, norm, rows8, unr8, blocks8, threads8, lds8, s); break;
-      case CHATTS_EPI_SWIGLU: launch8_norm<CHATTS_EPI_SWIGLU>(p, norm, rows8, unr8, blocks8, threads8, lds8, s); break;
-      default: launch8_norm<CHATTS_EPI_NONE>(p, norm, rows8, unr8, blocks8, threads8, lds8, s); break;
-    }
-    CHATTS_CHECK_LAUNCH("gemv8_ldsx");
-    return CHATTS_OK;
-  }
+  // (the bound is on the bf16 staging of x for every format, as it has always been; no supported K comes near it)
+  CHATTS_REQUIRE((size_t)nchunks * 512 * 4 + 64 * 4 <= 160 * 1024, CHATTS_E_SHAPE, "gemv: K=%d too large for the LDS-resident x", a->k);
+  const GemvFormat fmt = a->w4 != nullptr ? kInt4 : a->w8 != nullptr ? kW8 : kBf16;       // 4-bit codes win over an 8-bit copy
+  const GemvGeometry g = gemv_geometry(a, fmt, cus);
+  p.tasks = g.tasks;
   // K-split form (see gemv_ksplit_kernel): when the row groups alone leave the chip nearly empty - fewer than ~6 waves per CU - and a
   // row is long enough to split.  Every TP = 1 shape of the supported models has >= 10 waves per CU and keeps the whole-K kernel.
-  p.ks = 1;
-  if (!a->tp_reduce && rows == 2 && unr == 2 && nchunks >= 4) {
-    int ks = gemv_pick_ksplit(p.tasks, nchunks, norm, (double)a->n * a->k * 2.0, cus);
+  if (fmt == kBf16 && !a->tp_reduce && g.rows == 2 && g.unr == 2 && nchunks >= 4) {
+    int ks = gemv_pick_ksplit(g.tasks, nchunks, norm, (double)a->n * a->k * 2.0, cus);
     ks = opt_get(OPT_GEMV_KS, ks);
     if (ks > 16) ks = 16;
     if (ks > 1) {
-      int groups = 16 / ks;
-      if (groups < 1) groups = 1;
-      const int nwk = groups * ks;
-      int blocksk = (p.tasks + groups - 1) / groups;
-      const int occk = (int)((150 * 1024) / lds) < 32 / nwk ? (int)((150 * 1024) / lds) : 32 / nwk;
-      if (blocksk > cus * (occk < 1 ? 1 : occk)) blocksk = cus * (occk < 1 ? 1 : occk);
+      const int groups = 16 / ks, nwk = groups * ks;            // as many row groups as fit in 16 waves
+      const size_t lds = (size_t)nchunks * 512 * 4 + 64 * 4;    // (never padded: GEMV_LDSPAD shapes the whole-K grid)
+      int occk = (int)((150 * 1024) / lds) < 32 / nwk ? (int)((150 * 1024) / lds) : 32 / nwk;
+      if (occk < 1) occk = 1;
+      int blocksk = (g.tasks + groups - 1) / groups;
+      if (blocksk > cus * occk) blocksk = cus * occk;
       p.ks = ks;
-      const dim3 g(blocksk), b(nwk * 64);
-      switch (epilogue) {
-        case CHATTS_EPI_RESID:
-          if (norm) hipLaunchKernelGGL((gemv_ksplit_kernel<CHATTS_EPI_RESID, true>), g, b, lds, s, p);
-          else hipLaunchKernelGGL((gemv_ksplit_kernel<CHATTS_EPI_RESID, false>), g, b, lds, s, p);
-          break;
-        case CHATTS_EPI_SWIGLU:
-          if (norm) hipLaunchKernelGGL((gemv_ksplit_kernel<CHATTS_EPI_SWIGLU, true>), g, b, lds, s, p);
-          else hipLaunchKernelGGL((gemv_ksplit_kernel<CHATTS_EPI_SWIGLU, false>), g, b, lds, s, p);
-          break;
-        default:
-          if (norm) hipLaunchKernelGGL((gemv_ksplit_kernel<CHATTS_EPI_NONE, true>), g, b, lds, s, p);
-          else hipLaunchKernelGGL((gemv_ksplit_kernel<CHATTS_EPI_NONE, false>), g, b, lds, s, p);
-          break;
-      }
+      gemv_dispatch<KSplit>(p, epilogue, norm, blocksk, nwk * 64, lds, s);
       CHATTS_CHECK_LAUNCH("gemv_ksplit");
       return CHATTS_OK;
     }
   }
-  if (a->tp_reduce) p.tp = tp_issue(a->tp_reduce, false);
-  if (rows == 4 && unr == 2) launch_ldsx<4, 2>(p, epilogue, norm, blocks, threads, lds_launch, s);
-  else if (rows == 4) launch_ldsx<4, 4>(p, epilogue, norm, blocks, threads, lds_launch, s);
-  else if (unr == 2) launch_ldsx<2, 2>(p, epilogue, norm, blocks, threads, lds_launch, s);
-  else launch_ldsx<2, 4>(p, epilogue, norm, blocks, threads, lds_launch, s);
-  CHATTS_CHECK_LAUNCH("gemv_ldsx");
+  if (a->tp_reduce) p.tp = tp_issue(a->tp_reduce, false);      // (after the last check that can refuse the call: one issue per launch)
+  if (fmt == kInt4) {
+    gemv_dispatch<KInt4>(p, epilogue, norm, g.blocks, g.threads, g.lds, s);
+    CHATTS_CHECK_LAUNCH("gemv4_ldsx");
+  } else if (fmt == kW8) {
+    if (p.w8_format == CHATTS_W8_INT8) gemv_dispatch_w8<true>(p, g, epilogue, norm, s);
+    else gemv_dispatch_w8<false>(p, g, epilogue, norm, s);
+    CHATTS_CHECK_LAUNCH("gemv8_ldsx");
+  } else {
+    if (g.rows == 4 && g.unr == 2) gemv_dispatch<KBf16<4, 2>>(p, epilogue, norm, g.blocks, g.threads, g.lds, s);
+    else if (g.rows == 4) gemv_dispatch<KBf16<4, 4>>(p, epilogue, norm, g.blocks, g.threads, g.lds, s);
+    else if (g.unr == 2) gemv_dispatch<KBf16<2, 2>>(p, epilogue, norm, g.blocks, g.threads, g.lds, s);
+    else gemv_dispatch<KBf16<2, 4>>(p, epilogue, norm, g.blocks, g.threads, g.lds, s);
+    CHATTS_CHECK_LAUNCH("gemv_ldsx");
+  }
   return CHATTS_OK;
 }
 
@@ -811,9 +688,6 @@ int launch_gemv(const ChattsLinearArgs* a, hipStream_t s) {
 // host-only query (no device touched): the K-split factor the bf16 decode GEMV picks for a shape on this device - see gemv_pick_ksplit
 extern "C" int chatts_gemv_ksplit(int n, int k, int epilogue, int has_norm) {
   if (n <= 0 || k <= 0) return -1;
-  const int swiglu = epilogue == CHATTS_EPI_SWIGLU;
-  const int units = swiglu ? n / 2 : n, upt = swiglu ? 1 : 2;
   const int cus = chatts::device_cus() > 0 ? chatts::device_cus() : 256;
-  return chatts::gemv_pick_ksplit((units + upt - 1) / upt, (k + 511) / 512, has_norm != 0, (double)n * k * 2.0, cus);
+  return chatts::gemv_pick_ksplit(chatts::gemv_tasks(n, epilogue, 2), (k + 511) / 512, has_norm != 0, (double)n * k * 2.0, cus);
 }
-

@@ -1,5 +1,5 @@
-// gemv_common.h - the arithmetic of the batch-1 weight-streaming GEMV, shared by gemv.hip and decode_mega.hip so that both
-// accumulate a row in exactly the same order (bit-identical results).
+// gemv_common.h - the arithmetic of the batch-1 weight-streaming GEMV (gemv.hip) that fixes the bits of a result: the FMA order of a
+// bf16 load, the contraction pattern of the RMSNorm sum of squares, SiLU, and the row map of a task.
 #pragma once
 #include "common.h"
 
@@ -33,9 +33,5 @@ __device__ __forceinline__ int task_row(int task, int r) {
   }
   return task * ROWS + r;
 }
-
-
-// host: default waves per workgroup / workgroups per CU of the stand-alone bf16 GEMV (gemv.hip)
-void gemv_default_geometry(int n, int k, int epilogue, int cus, int* nw_out, int* occ_out);
 
 }  // namespace chatts
