@@ -11,8 +11,18 @@
 //    from LDS).  Softmax statistics are wave shuffles; P is broadcast lane->wave with v_readlane.
 //    Each wave emits an (m, l, o[G][128]) partial; attn_decode_combine_kernel merges the partials of a head.
 //  * attn_rows_kernel (short prefill chunks, T < 16, and the last-row path): one workgroup per (kv head, query row), 64-key
-//    tiles, online softmax, float32 VALU.  Longer chunks run the flash kernels further down: attn_prefill_bf16x3_kernel (bf16
-//    matrix pipe on hi / lo planes, the default) and attn_prefill_mfma_kernel (exact-f32 MFMA).
+//    tiles, online softmax, float32 VALU; attn_combine_kernel merges its key splits (attn_store<1>).
+//  * the flash kernels of longer chunks (T >= 16), one workgroup per (64 query rows, query head), built from attn_prefill.h:
+//      attn_prefill_bf16x3_kernel  bf16 matrix pipe on hi / lo planes split while the tile is staged (the default without a workspace):
+//                                  FlashTile, load_q_split, split_hi_lo, mfma3<false>, flash_softmax_rows<2, false>,
+//                                  flash_store_row<16> (attn_store<1> / attn_store_partial<16>)
+//      kv_planes_kernel            K / V of the sequence split into bf16 hi / lo planes once per layer and chunk: tile_row, split_hi_lo
+//      attn_prefill_planes_kernel  the flash loop on those planes, transposed (the default with a workspace): mfma3<true>, softmax_shift,
+//                                  split_hi_lo; its setup, Q load and store stay written out (with them shared
+//                                  the kernel measured 0.3 - 0.5 us slower; as it stands its instruction stream is unchanged)
+//      attn_prefill_mfma_kernel    exact-f32 MFMA (option ATTN_BF16X3=0, a debugging aid): FlashTile, flash_softmax_rows<2, true>,
+//                                  flash_store_row<1> (attn_store<8> / attn_store_partial<1>)
+//    attn_combine_rows_kernel merges their key splits (attn_store<4>).
 // The KV cache is float32 by default: the parity target is the float32 reference path and the cache
 // is ~1% of decode traffic at the benchmark context.  An fp16 cache (ChattsKvCache.dtype = CHATTS_KV_F16) is
 // the opt-in speed mode: every kernel that reads or writes the cache is a template on its element type KV (float instantiations =
@@ -21,11 +31,8 @@
 #include <math.h>
 
 #include "common.h"
-
-namespace chatts {
-
-}  // namespace chatts
 #include "attn_decode.h"
+#include "attn_prefill.h"
 namespace chatts {
 
 // ---------------------------------------------------------------------------------------------------
@@ -206,26 +213,18 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
   __shared__ __attribute__((aligned(16))) float v_s[KT * VS];
   __shared__ __attribute__((aligned(16))) float k_s[KT * KS];
   __shared__ float p_all[4 * 16 * PS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int hq = blockIdx.y;
-  const int G = p.n_q / p.n_kv, hk = hq / G;
-  const int heads = p.n_q + 2 * p.n_kv;
-  const int T = p.t, pos0 = p.pos0_dev ? *p.pos0_dev : p.pos0;
-  const int qt = gridDim.x - 1 - blockIdx.x;                // heaviest query tiles (most key tiles) first
-  const int q0 = qt * 64;
-  const int arow = lane & 15, kq = lane >> 4;              // A/B fragment coordinates
-  const int ccol = lane & 15, crow0 = (lane >> 4) * 4;     // C layout
-  const float scale2 = 0.08838834764831845f * 1.4426950408889634f;   // d^-1/2 * log2(e): the softmax runs on exp2
-  float* p_s = p_all + wave * 16 * PS;
+  const FlashTile<KT> ft(p, gridDim.x - 1 - blockIdx.x, blockIdx.y, attn_pos0(p));   // heaviest query tiles (most key tiles) first
+  const int tid = ft.tid, hq = ft.hq;
+  const int arow = ft.fi, kq = ft.fg;                       // A/B fragment coordinates
+  const int ccol = ft.fi, crow0 = ft.fg * 4;                // C layout
+  float* p_s = p_all + ft.wave * 16 * PS;
 
   float qreg[32];
   {
-    int qrow = q0 + wave * 16 + arow;
-    if (qrow > T - 1) qrow = T - 1;                         // padded rows compute garbage that is never stored
     // K-slot assignment: the MFMA's K index is free as long as both operands agree, so lane group kq takes head dims
     // kq*32 .. kq*32+31 (contiguous: the K fragments below are ds_read_b128, four MFMAs per read), visiting its eight
     // 4-float chunks rotated by kq & 1 - the rotation that makes the b128 reads of the [KT][136] tile conflict-free.
-    const float* qp = p.qkv + ((size_t)qrow * heads + hq) * kHeadDim + kq * 32;
+    const float* qp = p.qkv + ((size_t)ft.qrow(arow) * ft.heads + hq) * kHeadDim + kq * 32;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const f32x4 qv = *reinterpret_cast<const f32x4*>(qp + 4 * ((i + (kq & 1)) & 7));
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
   }
   int qpos[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) qpos[r] = pos0 + q0 + wave * 16 + crow0 + r;
+  for (int r = 0; r < 4; ++r) qpos[r] = ft.qpos(crow0 + r);
   float m_run[4], l_run[4];
   f32x4 o_acc[8];
 #pragma unroll
@@ -242,21 +241,15 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
 #pragma unroll
   for (int db = 0; db < 8; ++db) o_acc[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int last_q = q0 + 63 < T - 1 ? q0 + 63 : T - 1;
-  const int kmax = pos0 + last_q;                           // last key any row of this workgroup may see
-  const int nkt = kmax / KT + 1;
   const KvLayout kvl{p.table, p.n_kv, p.max_ctx, p.log_block};
-
-  // K/V tiles go global -> registers -> LDS; the loads of tile kt+1 are issued BEFORE the MFMAs of tile kt, so their L2
-  // latency hides under the tile's 128 MFMAs per wave instead of sitting between two barriers.
   constexpr int SLOTS = KT * 32 / 256;                      // float4 slots per thread and operand
   f32x4 kreg[SLOTS], vreg[SLOTS];
   auto load_tile = [&](int kt) {
-    const size_t toff = kv_tile_off(kvl, hk, kt * KT);      // first row of the tile (one block-table lookup when paged)
+    const size_t toff = kv_tile_off(kvl, ft.hk, kt * KT);   // first row of the tile (one block-table lookup when paged)
 #pragma unroll
     for (int i = 0; i < SLOTS; ++i) {
       const int idx = tid + i * 256, key = idx >> 5, c4 = idx & 31;
-      const int kr = kt * KT + key <= kmax ? key : kmax - kt * KT;    // clamped row inside the tile; masked by key index below
+      const int kr = ft.tile_row(kt, key);
       kreg[i] = *reinterpret_cast<const f32x4*>(p.kc + toff + (size_t)kr * kHeadDim + c4 * 4);
       vreg[i] = *reinterpret_cast<const f32x4*>(p.vc + toff + (size_t)kr * kHeadDim + c4 * 4);
     }
@@ -271,7 +264,9 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
   };
   // Key split (flash-decoding style): workgroup z takes key tiles z, z + NS, ...  T/16 x heads waves is all the parallelism one
   // sequence has (~2 waves per SIMD at T = 798, and the causal mask makes them unequal); splitting the keys doubles it.
-  const int NS = p.n_splits, split = blockIdx.z;
+  // K/V tiles go global -> registers -> LDS; the loads of tile kt+NS are issued BEFORE the MFMAs of tile kt, so their L2
+  // latency hides under the tile's 128 MFMAs per wave instead of sitting between two barriers.
+  const int NS = p.n_splits, split = blockIdx.z, nkt = ft.nkt;
   if (split < nkt) load_tile(split);
   for (int kt = split; kt < nkt; kt += NS) {
     const int k0 = kt * KT;
@@ -295,54 +290,8 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
         for (int nb = 0; nb < NB; ++nb)
           s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[4 * i + e], kf[nb][e], s_acc[nb], 0, 0, 0);
     }
-    // Online softmax in the log2 domain (scores are pre-scaled by d^-1/2 * log2 e, so every exponential is one v_exp_f32),
-    // written stage by stage over the four rows a lane holds: the DPP reductions are dependent chains with wait states,
-    // and four independent chains in flight are what hides them (measured with s_memtime: this block was 3.5k cycles per
-    // tile as a per-row loop with expf, against 2k cycles for the 64 MFMAs of Q.K^T).
-    float mx[4], ps[4], alpha[4], m_ref[4];
-    const bool diag = k0 + KT - 1 > pos0 + q0 + wave * 16;  // wave-uniform: only such a tile holds keys some row of this wave cannot see
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      mx[r] = -INFINITY;
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        float sc = s_acc[nb][r] * scale2;
-        if (diag && k0 + nb * 16 + ccol > qpos[r]) sc = -INFINITY;  // causal mask
-        s_acc[nb][r] = sc;
-        mx[r] = fmaxf(mx[r], sc);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], lane_xor1(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], lane_xor2(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], row_ror4(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], row_ror8(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float m_new = fmaxf(m_run[r], mx[r]);
-      // a key split other than 0 may start on a tile this row cannot see at all: keep m = -inf, contribute nothing
-      m_ref[r] = m_new == -INFINITY ? 0.f : m_new;
-      alpha[r] = __builtin_amdgcn_exp2f(m_run[r] - m_ref[r]);
-      m_run[r] = m_new;
-      ps[r] = 0.f;
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        const float e = __builtin_amdgcn_exp2f(s_acc[nb][r] - m_ref[r]);
-        s_acc[nb][r] = e;
-        ps[r] += e;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += lane_xor1(ps[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += lane_xor2(ps[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += row_ror4(ps[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += row_ror8(ps[r]);
+    float alpha[4], ps[4];
+    flash_softmax_rows<NB, true>(s_acc, k0, ccol, qpos, m_run, ps, alpha, ft.diag(k0));
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       l_run[r] = l_run[r] * alpha[r] + ps[r];
@@ -367,35 +316,11 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int qrow = q0 + wave * 16 + crow0 + r;
-    if (qrow < T && NS > 1) {                               // partial (unnormalised) result of this key split
-      const size_t pi = ((size_t)qrow * p.n_q + hq) * NS + split;
-      float* dst = p.part_o + pi * kHeadDim + ccol * 8;
-      *reinterpret_cast<f32x4*>(dst) = (f32x4){o_acc[0][r], o_acc[1][r], o_acc[2][r], o_acc[3][r]};
-      *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){o_acc[4][r], o_acc[5][r], o_acc[6][r], o_acc[7][r]};
-      if (ccol == 0) { p.part_ml[pi * 2] = m_run[r] * 0.6931471805599453f; p.part_ml[pi * 2 + 1] = l_run[r]; }   // m back to nats
-    } else if (qrow < T) {
-      const float inv = 1.0f / l_run[r];
-      const size_t oi = ((size_t)qrow * p.n_q + hq) * kHeadDim + ccol * 8;
-      if (p.out_hi) {
-        typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-        bf16x8v hv, lv;
-#pragma unroll
-        for (int db = 0; db < 8; ++db) {
-#pragma clang fp contract(off)   // lo = split of the ROUNDED product, as chatts_split_bf16x2 of the float32 output would give
-          const float v = o_acc[db][r] * inv;
-          const __bf16 h = (__bf16)v;
-          hv[db] = h;
-          lv[db] = (__bf16)(v - (float)h);
-        }
-        *reinterpret_cast<bf16x8v*>(p.out_hi + oi) = hv;
-        *reinterpret_cast<bf16x8v*>(p.out_lo + oi) = lv;
-      } else {
-        float* dst = p.out + oi;
-        *reinterpret_cast<f32x4*>(dst) = (f32x4){o_acc[0][r] * inv, o_acc[1][r] * inv, o_acc[2][r] * inv, o_acc[3][r] * inv};
-        *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){o_acc[4][r] * inv, o_acc[5][r] * inv, o_acc[6][r] * inv, o_acc[7][r] * inv};
-      }
-    }
+    const int qrow = ft.wrow0 + crow0 + r;
+    if (qrow >= ft.T) continue;
+    const float o[8] = {o_acc[0][r], o_acc[1][r], o_acc[2][r], o_acc[3][r],
+                        o_acc[4][r], o_acc[5][r], o_acc[6][r], o_acc[7][r]};
+    flash_store_row<1>(p, qrow, hq, split, ccol * 8, o, ccol == 0, m_run[r], l_run[r]);
   }
 }
 
@@ -409,18 +334,6 @@ __global__ __launch_bounds__(256, 3) void attn_prefill_mfma_kernel(AttnParams p)
 // operand of P.V needs 8 consecutive KEYS of one head dim per lane - the staging threads of V therefore vary over keys
 // within a wave (contiguous 2-byte LDS writes) and pay with 16-byte global reads at a 512-byte stride (L2-resident rows).
 // ---------------------------------------------------------------------------------------------------
-typedef __bf16 abf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 abf16x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split8(const float (&x)[8], abf16x8_t& hi, abf16x8_t& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)x[j];
-    hi[j] = h;
-    lo[j] = (__bf16)(x[j] - (float)h);
-  }
-}
-
 template <typename KV>
 __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams p) {
   constexpr int KT = 32, NB = 2, KROW = 272, VROW = 80, PS = 36;
@@ -429,33 +342,17 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
   __shared__ __attribute__((aligned(16))) char vt_hi[kHeadDim * VROW];
   __shared__ __attribute__((aligned(16))) char vt_lo[kHeadDim * VROW];
   __shared__ __attribute__((aligned(16))) float p_all[4 * 16 * PS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int hq = blockIdx.y;
-  const int G = p.n_q / p.n_kv, hk = hq / G;
-  const int heads = p.n_q + 2 * p.n_kv;
-  const int T = p.t, pos0 = p.pos0_dev ? *p.pos0_dev : p.pos0;
-  const int qt = gridDim.x - 1 - blockIdx.x;                // heaviest query tiles (most key tiles) first
-  const int q0 = qt * 64;
-  const int arow = lane & 15, kq = lane >> 4;              // A/B fragment coordinates: row / column, group of 8 K-values
-  const int ccol = lane & 15, crow0 = (lane >> 4) * 4;     // C layout
-  const float scale2 = 0.08838834764831845f * 1.4426950408889634f;   // d^-1/2 * log2(e): the softmax runs on exp2
-  float* p_s = p_all + wave * 16 * PS;
+  const FlashTile<KT> ft(p, gridDim.x - 1 - blockIdx.x, blockIdx.y, attn_pos0(p));   // heaviest query tiles (most key tiles) first
+  const int tid = ft.tid, hq = ft.hq;
+  const int arow = ft.fi, kq = ft.fg;                       // A/B fragment coordinates: row / column, group of 8 K-values
+  const int ccol = ft.fi, crow0 = ft.fg * 4;                // C layout
+  float* p_s = p_all + ft.wave * 16 * PS;
 
   abf16x8_t q_hi[4], q_lo[4];                                // A fragments of this wave's 16 query rows, 4 K-steps of 32 dims
-  {
-    int qrow = q0 + wave * 16 + arow;
-    if (qrow > T - 1) qrow = T - 1;                         // padded rows compute garbage that is never stored
-    const float* qp = p.qkv + ((size_t)qrow * heads + hq) * kHeadDim + kq * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(qp + ks * 32), b = *reinterpret_cast<const f32x4*>(qp + ks * 32 + 4);
-      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      split8(x, q_hi[ks], q_lo[ks]);
-    }
-  }
+  load_q_split(p, ft.qrow(arow), ft.heads, hq, kq, q_hi, q_lo);
   int qpos[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) qpos[r] = pos0 + q0 + wave * 16 + crow0 + r;
+  for (int r = 0; r < 4; ++r) qpos[r] = ft.qpos(crow0 + r);
   float m_run[4], l_run[4];
   f32x4 o_acc[8];
 #pragma unroll
@@ -463,35 +360,26 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
 #pragma unroll
   for (int db = 0; db < 8; ++db) o_acc[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int last_q = q0 + 63 < T - 1 ? q0 + 63 : T - 1;
-  const int kmax = pos0 + last_q;                           // last key any row of this workgroup may see
-  const int nkt = kmax / KT + 1;
   const KvLayout kvl{p.table, p.n_kv, p.max_ctx, p.log_block};
-
-  // tile kt+1 is loaded into registers before the MFMAs of tile kt (as in the float32 kernel).
   // K: thread (key = idx >> 5, 4 dims idx & 31): a wave reads two whole key rows.  V: a lane takes the SAME 4 dims of the key
   // pair (2j, 2j+1), j = lane & 15, so that the transposed store is one 4-byte write per dim - the two keys' bf16 values side
   // by side, 16 lanes = 16 consecutive dwords (the first version wrote 2 bytes per lane: 35 % of all LDS cycles were conflicts).
   typename KvVec4<KV>::T kreg[4], vreg[4];                   // as loaded (fp16: widened in store_tile, after the MFMAs of the tile before)
-  const int vj = lane & 15;
+  const int vj = ft.lane & 15;
   auto load_tile = [&](int kt) {
-    const size_t toff = kv_tile_off(kvl, hk, kt * KT);      // first row of the tile (one block-table lookup when paged)
+    const size_t toff = kv_tile_off(kvl, ft.hk, kt * KT);   // first row of the tile (one block-table lookup when paged)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * 256;
       const int kkey = idx >> 5, kc4 = idx & 31;
-      const int kr = kt * KT + kkey <= kmax ? kkey : kmax - kt * KT;    // clamped row inside the tile; masked by key index below
-      kreg[i] = kv_load4(kv_ptr<KV>(p.kc) + toff + (size_t)kr * kHeadDim + kc4 * 4);
+      kreg[i] = kv_load4(kv_ptr<KV>(p.kc) + toff + (size_t)ft.tile_row(kt, kkey) * kHeadDim + kc4 * 4);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int vc4 = (tid >> 4) + 16 * i;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int vkey = 2 * vj + h;
-        const int vr = kt * KT + vkey <= kmax ? vkey : kmax - kt * KT;
-        vreg[2 * i + h] = kv_load4(kv_ptr<KV>(p.vc) + toff + (size_t)vr * kHeadDim + vc4 * 4);
-      }
+      for (int h = 0; h < 2; ++h)
+        vreg[2 * i + h] = kv_load4(kv_ptr<KV>(p.vc) + toff + (size_t)ft.tile_row(kt, 2 * vj + h) * kHeadDim + vc4 * 4);
     }
   };
   auto store_tile = [&]() {
@@ -499,36 +387,27 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * 256;
       const int kkey = idx >> 5, kc4 = idx & 31;
-      const f32x4 kw = kv_widen4(kreg[i]);
-      const float kx[4] = {kw.x, kw.y, kw.z, kw.w};
       abf16x4_t kh, kl;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 h = (__bf16)kx[e];
-        kh[e] = h;
-        kl[e] = (__bf16)(kx[e] - (float)h);
-      }
+      split_hi_lo(kv_widen4(kreg[i]), kh, kl);
       *reinterpret_cast<abf16x4_t*>(k_hi + kkey * KROW + kc4 * 8) = kh;
       *reinterpret_cast<abf16x4_t*>(k_lo + kkey * KROW + kc4 * 8) = kl;
     }
-    typedef __bf16 abf16x2_t __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int vc4 = (tid >> 4) + 16 * i;
       const f32x4 w0 = kv_widen4(vreg[2 * i]), w1 = kv_widen4(vreg[2 * i + 1]);
-      const float v0[4] = {w0.x, w0.y, w0.z, w0.w};
-      const float v1[4] = {w1.x, w1.y, w1.z, w1.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        const float pair[2] = {w0[e], w1[e]};
         abf16x2_t h, l;
-        h[0] = (__bf16)v0[e]; h[1] = (__bf16)v1[e];
-        l[0] = (__bf16)(v0[e] - (float)h[0]); l[1] = (__bf16)(v1[e] - (float)h[1]);
+        split_hi_lo(pair, h, l);
         *reinterpret_cast<abf16x2_t*>(vt_hi + (vc4 * 4 + e) * VROW + vj * 4) = h;
         *reinterpret_cast<abf16x2_t*>(vt_lo + (vc4 * 4 + e) * VROW + vj * 4) = l;
       }
     }
   };
-  const int NS = p.n_splits, split = blockIdx.z;
+  // tile kt+NS is loaded into registers before the MFMAs of tile kt (as in the float32 kernel)
+  const int NS = p.n_splits, split = blockIdx.z, nkt = ft.nkt;
   if (split < nkt) load_tile(split);
   for (int kt = split; kt < nkt; kt += NS) {
     const int k0 = kt * KT;
@@ -536,9 +415,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
     store_tile();
     __syncthreads();
     if (kt + NS < nkt) load_tile(kt + NS);
-    // the workgroup walks the keys its LAST query row sees; a wave whose 16 rows all lie before this tile has nothing to add
-    // (every score masked): wave-uniform skip, the barriers above keep the cadence
-    if (k0 > pos0 + q0 + wave * 16 + 15) continue;
+    if (!ft.wave_sees(k0)) continue;                        // every score masked: wave-uniform skip, the barriers above keep the cadence
 
     f32x4 s_acc[NB];
 #pragma unroll
@@ -548,56 +425,12 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const int off = (nb * 16 + arow) * KROW + ks * 64 + kq * 16;
-        const abf16x8_t bh = *reinterpret_cast<const abf16x8_t*>(k_hi + off);
-        const abf16x8_t bl = *reinterpret_cast<const abf16x8_t*>(k_lo + off);
-        s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_lo[ks], bh, s_acc[nb], 0, 0, 0);
-        s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_hi[ks], bl, s_acc[nb], 0, 0, 0);
-        s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_hi[ks], bh, s_acc[nb], 0, 0, 0);
+        mfma3<false>(q_hi[ks], q_lo[ks], *reinterpret_cast<const abf16x8_t*>(k_hi + off), *reinterpret_cast<const abf16x8_t*>(k_lo + off),
+                     s_acc[nb]);
       }
     }
-    // online softmax in the log2 domain: identical to attn_prefill_mfma_kernel (C layout: column = key, 4 rows per lane)
-    float mx[4], ps[4], alpha[4], m_ref[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      mx[r] = -INFINITY;
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        float sc = s_acc[nb][r] * scale2;
-        if (k0 + nb * 16 + ccol > qpos[r]) sc = -INFINITY;  // causal mask
-        s_acc[nb][r] = sc;
-        mx[r] = fmaxf(mx[r], sc);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], lane_xor1(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], lane_xor2(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], row_ror4(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], row_ror8(mx[r]));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float m_new = fmaxf(m_run[r], mx[r]);
-      m_ref[r] = m_new == -INFINITY ? 0.f : m_new;           // a key split may start on a tile this row cannot see at all
-      alpha[r] = __builtin_amdgcn_exp2f(m_run[r] - m_ref[r]);
-      m_run[r] = m_new;
-      ps[r] = 0.f;
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        const float e = __builtin_amdgcn_exp2f(s_acc[nb][r] - m_ref[r]);
-        s_acc[nb][r] = e;
-        ps[r] += e;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += lane_xor1(ps[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += lane_xor2(ps[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += row_ror4(ps[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ps[r] += row_ror8(ps[r]);
+    float alpha[4], ps[4];
+    flash_softmax_rows<NB, false>(s_acc, k0, ccol, qpos, m_run, ps, alpha);
     // no running maximum of this wave's rows moved (every alpha == 1.0f exactly): the 32 rescaling multiplies would change nothing
     const bool moved = __builtin_amdgcn_ballot_w64(alpha[0] != 1.f || alpha[1] != 1.f || alpha[2] != 1.f || alpha[3] != 1.f) != 0;
 #pragma unroll
@@ -616,47 +449,23 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_bf16x3_kernel(AttnParams 
     __builtin_amdgcn_wave_barrier();                        // P is wave private: LDS ops of one wave stay in order
     // P as the A operand of P.V: query row arow, keys kq*8 .. kq*8+7 (two conflict-free ds_read_b128 of the [16][36] tile)
     abf16x8_t p_hi, p_lo;
-    {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p_s + arow * PS + kq * 8), b = *reinterpret_cast<const f32x4*>(p_s + arow * PS + kq * 8 + 4);
-      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      split8(x, p_hi, p_lo);
-    }
+    split_hi_lo(*reinterpret_cast<const f32x4*>(p_s + arow * PS + kq * 8), *reinterpret_cast<const f32x4*>(p_s + arow * PS + kq * 8 + 4),
+                p_hi, p_lo);
 #pragma unroll
     for (int db = 0; db < 8; ++db) {                        // head dims db*16 .. db*16+15: B fragment = 8 keys of dim db*16 + arow
       const int off = (db * 16 + arow) * VROW + kq * 16;
-      const abf16x8_t vh = *reinterpret_cast<const abf16x8_t*>(vt_hi + off);
-      const abf16x8_t vl = *reinterpret_cast<const abf16x8_t*>(vt_lo + off);
-      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p_lo, vh, o_acc[db], 0, 0, 0);
-      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p_hi, vl, o_acc[db], 0, 0, 0);
-      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p_hi, vh, o_acc[db], 0, 0, 0);
+      mfma3<false>(p_hi, p_lo, *reinterpret_cast<const abf16x8_t*>(vt_hi + off), *reinterpret_cast<const abf16x8_t*>(vt_lo + off),
+                   o_acc[db]);
     }
   }
   // C layout of the output: lane holds head dims db*16 + ccol (db = 0..7) of query rows crow0 + r
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int qrow = q0 + wave * 16 + crow0 + r;
-    if (qrow >= T) continue;
-    if (NS > 1) {                                           // partial (unnormalised) result of this key split
-      const size_t pi = ((size_t)qrow * p.n_q + hq) * NS + split;
-#pragma unroll
-      for (int db = 0; db < 8; ++db) p.part_o[pi * kHeadDim + db * 16 + ccol] = o_acc[db][r];
-      if (ccol == 0) { p.part_ml[pi * 2] = m_run[r] * 0.6931471805599453f; p.part_ml[pi * 2 + 1] = l_run[r]; }   // m back to nats
-    } else {
-      const float inv = 1.0f / l_run[r];
-      const size_t oi = ((size_t)qrow * p.n_q + hq) * kHeadDim;
-#pragma unroll
-      for (int db = 0; db < 8; ++db) {
-#pragma clang fp contract(off)   // lo = split of the ROUNDED product, as chatts_split_bf16x2 of the float32 output would give
-        const float v = o_acc[db][r] * inv;
-        if (p.out_hi) {
-          const __bf16 h = (__bf16)v;
-          p.out_hi[oi + db * 16 + ccol] = __builtin_bit_cast(uint16_t, h);
-          p.out_lo[oi + db * 16 + ccol] = __builtin_bit_cast(uint16_t, (__bf16)(v - (float)h));
-        } else {
-          p.out[oi + db * 16 + ccol] = v;
-        }
-      }
-    }
+    const int qrow = ft.wrow0 + crow0 + r;
+    if (qrow >= ft.T) continue;
+    const float o[8] = {o_acc[0][r], o_acc[1][r], o_acc[2][r], o_acc[3][r],
+                        o_acc[4][r], o_acc[5][r], o_acc[6][r], o_acc[7][r]};
+    flash_store_row<16>(p, qrow, hq, split, ccol, o, ccol == 0, m_run[r], l_run[r]);
   }
 }
 
@@ -688,16 +497,8 @@ __global__ __launch_bounds__(256) void kv_planes_kernel(AttnParams p, int n_keys
   for (int i = 0; i < 4; ++i) {                             // K: thread = (key, 4 dims), rows stay rows
     const int idx = tid + i * 256;
     const int key = idx >> 5, c4 = idx & 31;
-    const int kr = key <= last ? key : last;
-    const f32x4 v = kv_widen4(kv_load4(kv_ptr<KV>(p.kc) + toff + (size_t)kr * kHeadDim + c4 * 4));
-    const float x[4] = {v.x, v.y, v.z, v.w};
     abf16x4_t h, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const __bf16 hh = (__bf16)x[e];
-      h[e] = hh;
-      l[e] = (__bf16)(x[e] - (float)hh);
-    }
+    split_hi_lo(kv_widen4(kv_load4(kv_ptr<KV>(p.kc) + toff + (size_t)tile_row(0, key, last) * kHeadDim + c4 * 4)), h, l);
     *reinterpret_cast<abf16x4_t*>(dst + key * kHeadDim + c4 * 4) = h;
     *reinterpret_cast<abf16x4_t*>(dst + KT * kHeadDim + key * kHeadDim + c4 * 4) = l;
   }
@@ -706,16 +507,12 @@ __global__ __launch_bounds__(256) void kv_planes_kernel(AttnParams p, int n_keys
   const int d = tid & 127, kg = tid >> 7;
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
-    abf16x4_t h, l;
+    float x[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int key = kg * 16 + 4 * g + j;
-      const int vr = key <= last ? key : last;
-      const float x = (float)kv_ptr<KV>(p.vc)[toff + (size_t)vr * kHeadDim + d];
-      const __bf16 hh = (__bf16)x;
-      h[j] = hh;
-      l[j] = (__bf16)(x - (float)hh);
-    }
+    for (int j = 0; j < 4; ++j)
+      x[j] = (float)kv_ptr<KV>(p.vc)[toff + (size_t)tile_row(0, kg * 16 + 4 * g + j, last) * kHeadDim + d];
+    abf16x4_t h, l;
+    split_hi_lo(x, h, l);
     *reinterpret_cast<abf16x4_t*>(dst + 2 * KT * kHeadDim + d * KT + 8 * g + 4 * kg) = h;
     *reinterpret_cast<abf16x4_t*>(dst + 3 * KT * kHeadDim + d * KT + 8 * g + 4 * kg) = l;
   }
@@ -755,7 +552,6 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_planes_kernel(AttnParams 
   const int qt = p.units - 1 - xi;                          // heaviest query tiles (most key tiles) first, over ALL heads
   const int q0 = qt * 64;
   const int qi = lane & 15, g = lane >> 4;                  // this lane's query (of the wave's 16) and its group of 8 K-values / 4 C rows
-  const float scale2 = 0.08838834764831845f * 1.4426950408889634f;   // d^-1/2 * log2(e): the softmax runs on exp2
 
   abf16x8_t q_hi[4], q_lo[4];                                // B fragments of Q^T: query qi, dims ks*32 + g*8 .. +7
   {
@@ -766,7 +562,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_planes_kernel(AttnParams 
     for (int ks = 0; ks < 4; ++ks) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(qp + ks * 32), b = *reinterpret_cast<const f32x4*>(qp + ks * 32 + 4);
       const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      split8(x, q_hi[ks], q_lo[ks]);
+      split_hi_lo(x, q_hi[ks], q_lo[ks]);
     }
   }
   const int qpos = pos0 + q0 + wave * 16 + qi;
@@ -818,13 +614,12 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_planes_kernel(AttnParams 
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         const int off = (nb * 16 + qi) * KROW + (((ks * 4 + g) ^ qi) << 4);
-        const abf16x8_t ah = *reinterpret_cast<const abf16x8_t*>(k_hi + off);
-        const abf16x8_t al = *reinterpret_cast<const abf16x8_t*>(k_lo + off);
-        s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, q_lo[ks], s_acc[nb], 0, 0, 0);
-        s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, q_hi[ks], s_acc[nb], 0, 0, 0);
-        s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, q_hi[ks], s_acc[nb], 0, 0, 0);
+        mfma3<true>(q_hi[ks], q_lo[ks], *reinterpret_cast<const abf16x8_t*>(k_hi + off), *reinterpret_cast<const abf16x8_t*>(k_lo + off),
+                    s_acc[nb]);
       }
     }
+    // the online softmax of ONE row per lane: flash_softmax_rows' recurrence (softmax_shift) without its four-row DPP stages - the
+    // row's 8 keys sit in this lane and its three partner lanes
     const bool diag = k0 + KT - 1 > pos0 + q0 + wave * 16;  // wave-uniform: only such a tile holds keys some query of this wave cannot see
     float e[8];
     float mx = -INFINITY;
@@ -832,7 +627,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_planes_kernel(AttnParams 
     for (int nb = 0; nb < 2; ++nb) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float sc = s_acc[nb][r] * scale2;
+        float sc = s_acc[nb][r] * kScale2;
         if (diag && k0 + nb * 16 + 4 * g + r > qpos) sc = -INFINITY;   // causal mask
         e[nb * 4 + r] = sc;
         mx = fmaxf(mx, sc);
@@ -840,10 +635,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_planes_kernel(AttnParams 
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);
-    const float m_ref = m_new == -INFINITY ? 0.f : m_new;
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_ref);
-    m_run = m_new;
+    float alpha;
+    const float m_ref = softmax_shift(m_run, mx, alpha);
     float ps = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -858,15 +651,12 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_planes_kernel(AttnParams 
       }
     }
     abf16x8_t p_hi, p_lo;                                    // B fragment of P^T: slots 8 g .. 8 g + 7 of query qi
-    split8(e, p_hi, p_lo);
+    split_hi_lo(e, p_hi, p_lo);
 #pragma unroll
     for (int db = 0; db < 8; ++db) {                        // head dims db*16 .. db*16+15: A fragment = 8 slots of dim db*16 + qi
       const int off = (db * 16 + qi) * VROW + ((g ^ ((qi >> 2) & 2)) << 4);
-      const abf16x8_t vh = *reinterpret_cast<const abf16x8_t*>(vt_hi + off);
-      const abf16x8_t vl = *reinterpret_cast<const abf16x8_t*>(vt_lo + off);
-      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, p_lo, o_acc[db], 0, 0, 0);
-      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vl, p_hi, o_acc[db], 0, 0, 0);
-      o_acc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, p_hi, o_acc[db], 0, 0, 0);
+      mfma3<true>(p_hi, p_lo, *reinterpret_cast<const abf16x8_t*>(vt_hi + off), *reinterpret_cast<const abf16x8_t*>(vt_lo + off),
+                  o_acc[db]);
     }
   };
   load_tile(0, kreg[0], vreg[0]);
@@ -924,15 +714,8 @@ __global__ __launch_bounds__(128) void attn_combine_kernel(AttnParams p) {
     num = fmaf(w, p.part_o[(base + s) * kHeadDim + d], num);
     den = fmaf(w, p.part_ml[(base + s) * 2 + 1], den);
   }
-  const size_t oi = ((size_t)row * p.n_q + hq) * kHeadDim + d;
-  const float v = num / den;
-  if (p.out_hi) {                                 // the o_proj operand format, written where the value is made
-    const __bf16 h = (__bf16)v;
-    p.out_hi[oi] = __builtin_bit_cast(uint16_t, h);
-    p.out_lo[oi] = __builtin_bit_cast(uint16_t, (__bf16)(v - (float)h));
-  } else {
-    p.out[oi] = v;
-  }
+  const float v[1] = {num / den};
+  attn_store<1>(p, ((size_t)row * p.n_q + hq) * kHeadDim + d, v);
 }
 
 // Combine of the key-split MFMA prefill path (n_splits <= 4): one workgroup per query row, every thread merges float4s of
@@ -955,22 +738,8 @@ __global__ __launch_bounds__(256) void attn_combine_rows_kernel(AttnParams p) {
       num.x = fmaf(w, o.x, num.x); num.y = fmaf(w, o.y, num.y); num.z = fmaf(w, o.z, num.z); num.w = fmaf(w, o.w, num.w);
       den = fmaf(w, p.part_ml[(base + s) * 2 + 1], den);
     }
-    const size_t oi = ((size_t)row * p.n_q + hq) * kHeadDim + d4;
     const float v[4] = {num.x / den, num.y / den, num.z / den, num.w / den};
-    if (p.out_hi) {
-      typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-      bf16x4v hv, lv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        hv[j] = h;
-        lv[j] = (__bf16)(v[j] - (float)h);
-      }
-      *reinterpret_cast<bf16x4v*>(p.out_hi + oi) = hv;
-      *reinterpret_cast<bf16x4v*>(p.out_lo + oi) = lv;
-    } else {
-      *reinterpret_cast<f32x4*>(p.out + oi) = (f32x4){v[0], v[1], v[2], v[3]};
-    }
+    attn_store<4>(p, ((size_t)row * p.n_q + hq) * kHeadDim + d4, v);
   }
 }
 
@@ -990,6 +759,13 @@ static int bind_workspace(AttnParams& p, void* workspace, size_t workspace_bytes
   p.part_o = reinterpret_cast<float*>(workspace);
   p.part_ml = p.part_o + (size_t)p.t * p.n_q * p.n_splits * kHeadDim;
   return CHATTS_OK;
+}
+
+// f(KV{}) with the cache's element type as a tag: the one place that maps ChattsKvCache.dtype to a kernel instantiation
+template <typename F>
+static void kv_dispatch(const int kv_f16, F&& f) {
+  if (kv_f16) f(_Float16{});
+  else f(float{});
 }
 
 // cache -> kernel parameters; the block-paged form is validated here (every entry point goes through this)
@@ -1057,8 +833,9 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
     if (planes) {
       uint16_t* pl = static_cast<uint16_t*>(workspace);
       const int nqt = (t + 63) / 64;
-      if (p.kv_f16) hipLaunchKernelGGL(kv_planes_kernel<_Float16>, dim3(tiles, n_kv), dim3(256), 0, as_stream(stream), p, n_keys, pl);
-      else hipLaunchKernelGGL(kv_planes_kernel<float>, dim3(tiles, n_kv), dim3(256), 0, as_stream(stream), p, n_keys, pl);
+      kv_dispatch(p.kv_f16, [&](auto kv) {
+        hipLaunchKernelGGL(kv_planes_kernel<decltype(kv)>, dim3(tiles, n_kv), dim3(256), 0, as_stream(stream), p, n_keys, pl);
+      });
       CHATTS_CHECK_LAUNCH("kv_planes");
       p.kv_planes = pl; p.kv_plane_tiles = tiles;
       const bool xcd_on = opt_get(OPT_ATTN_XCD, 1) != 0;
@@ -1067,10 +844,11 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
       const int G = n_q / n_kv;
       const int grid = p.xcd_share ? 8 * ((G * p.units + p.xcd_share - 1) / p.xcd_share) : n_q * p.units;
       hipLaunchKernelGGL(attn_prefill_planes_kernel, dim3(grid), dim3(256), 0, as_stream(stream), p);
-    } else if (bf16x3 && p.kv_f16) {
-      hipLaunchKernelGGL(attn_prefill_bf16x3_kernel<_Float16>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
     } else if (bf16x3) {
-      hipLaunchKernelGGL(attn_prefill_bf16x3_kernel<float>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
+      kv_dispatch(p.kv_f16, [&](auto kv) {
+        hipLaunchKernelGGL(attn_prefill_bf16x3_kernel<decltype(kv)>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0,
+                           as_stream(stream), p);
+      });
     } else hipLaunchKernelGGL(attn_prefill_mfma_kernel<32>, dim3((t + 63) / 64, n_q, n_splits), dim3(256), 0, as_stream(stream), p);
     CHATTS_CHECK_LAUNCH("attn_prefill_mfma");
     if (n_splits > 1) {
@@ -1079,8 +857,9 @@ int chatts::attention_impl(const float* qkv, int t, int n_q, int n_kv, int pos0,
     }
     return CHATTS_OK;
   }
-  if (p.kv_f16) hipLaunchKernelGGL(attn_rows_kernel<_Float16>, dim3(n_kv, t, n_splits), dim3(256), 0, as_stream(stream), p);
-  else hipLaunchKernelGGL(attn_rows_kernel<float>, dim3(n_kv, t, n_splits), dim3(256), 0, as_stream(stream), p);
+  kv_dispatch(p.kv_f16, [&](auto kv) {
+    hipLaunchKernelGGL(attn_rows_kernel<decltype(kv)>, dim3(n_kv, t, n_splits), dim3(256), 0, as_stream(stream), p);
+  });
   CHATTS_CHECK_LAUNCH("attn_rows");
   if (n_splits > 1) {
     hipLaunchKernelGGL(attn_combine_kernel, dim3(n_q, t), dim3(128), 0, as_stream(stream), p);
@@ -1135,8 +914,7 @@ int attention_decode_batched_impl(const float* qkv_raw, int batch, int n_q, int 
   // built); option ATTN_EXACT=0: the run-time form
   const bool exact = opt_get(OPT_ATTN_EXACT, 1) != 0;
   const dim3 wave(64);
-  if (p.kv_f16) launch_decode<_Float16>(n_q / n_kv, exact, grid, wave, as_stream(stream), p);
-  else launch_decode<float>(n_q / n_kv, exact, grid, wave, as_stream(stream), p);
+  kv_dispatch(p.kv_f16, [&](auto kv) { launch_decode<decltype(kv)>(n_q / n_kv, exact, grid, wave, as_stream(stream), p); });
   CHATTS_CHECK_LAUNCH("attn_decode");
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(n_q, batch), dim3(128), 0, as_stream(stream), p);
   CHATTS_CHECK_LAUNCH("attn_decode_combine");

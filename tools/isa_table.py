@@ -1,17 +1,22 @@
 #!/usr/bin/env python
-"""What the compiler makes of two versions of csrc/gemv.hip, kernel by kernel (a COMPILE for gfx950, no device involved):
+"""What the compiler makes of two versions of one csrc/*.hip file, kernel by kernel (a COMPILE for gfx950, no device involved):
 
-    python tools/gemv_isa_table.py OLD_gemv.hip [NEW_gemv.hip] > profiles/gemv_unify_isa.txt
+    python tools/isa_table.py OLD_gemv.hip [NEW_gemv.hip] > profiles/gemv_unify_isa.txt
+    python tools/isa_table.py --source attention.hip --hot v_mfma OLD_attention.hip [NEW_attention.hip] > profiles/attention_unify_isa.txt
 
+--source names the file of csrc/ that NEW defaults to (gemv.hip), --hot the regular expression whose matches make a basic block a hot
+block (default: gemv.hip's non-temporal weight loads and FMA / dot instructions; for attention.hip the blocks that hold an MFMA).
 Both files are compiled with the library's flags plus -Rpass-analysis=kernel-resource-usage and --save-temps; a header next to a file
 wins over csrc/ (an old gemv.hip travels with its gemv_common.h).  One row per instantiation, joined by demangled name: VGPRs, SGPRs,
 scratch bytes per lane, occupancy (waves per SIMD), old -> new, and how the instruction streams compare after renaming labels:
     identical   the same instructions with the same registers
     registers   the same instructions, other register numbers
-    outside     differences outside the stream loop only: the basic blocks that hold the non-temporal weight loads or FMA / dot instructions
-                have the same opcode sequence (prologue / epilogue scheduling)
-    order       the stream loop holds the same instructions in another order (a compare and the branch on it may be inverted together)
-    HOT LOOP    the stream loop holds other instructions: their number, old -> new"""
+    outside     differences outside the hot blocks only: the basic blocks that hold a --hot instruction have the same opcode sequence
+                (prologue / epilogue scheduling)
+    order       the hot blocks hold the same instructions in another order (a compare and the branch on it may be inverted together)
+    HOT LOOP    the hot blocks hold other instructions: their number, old -> new, and which opcodes went (-) or came (+)"""
+import argparse
+import collections
 import os
 import re
 import subprocess
@@ -23,8 +28,8 @@ sys.path.insert(0, ROOT)
 from chatts_amd import build as b  # noqa: E402
 
 FIELDS = (("VGPRs", "VGPRs"), ("SGPRs", "TotalSGPRs"), ("scratch", "ScratchSize [bytes/lane]"), ("occ", "Occupancy [waves/SIMD]"))
-HOT = re.compile(r"\bnt\b|v_fma|v_pk_fma|v_dot2")          # the weight loads and the dot blocks (sumsq4 contracts to v_fmac too: its
-# block has no weight load, but it is the same code in both files and costs the comparison nothing)
+GEMV_HOT = r"\bnt\b|v_fma|v_pk_fma|v_dot2"      # the weight loads and the dot blocks (sumsq4 contracts to v_fmac too: its block has no
+# weight load, but it is the same code in both files and costs the comparison nothing)
 INVERSE = {"s_cmp_ge_i32": "s_cmp_lt_i32", "s_cmp_le_i32": "s_cmp_gt_i32", "v_cmp_le_i32_e32": "v_cmp_gt_i32_e32",
            "v_cmp_ge_i32_e32": "v_cmp_lt_i32_e32", "s_cbranch_scc0": "s_cbranch_scc1", "s_cbranch_vccz": "s_cbranch_vccnz"}
 REG = re.compile(r"\b[vsa](\d+|\[\d+:\d+\])")
@@ -33,7 +38,7 @@ REG = re.compile(r"\b[vsa](\d+|\[\d+:\d+\])")
 def compile_one(src, out):
     os.makedirs(out, exist_ok=True)
     cmd = [b._hipcc(), *b.FLAGS, "-I", os.path.dirname(os.path.abspath(src)), "-I", b.CSRC, "-Rpass-analysis=kernel-resource-usage",
-           "--save-temps", "-c", os.path.abspath(src), "-o", "gemv.o"]
+           "--save-temps", "-c", os.path.abspath(src), "-o", "unit.o"]
     r = subprocess.run(cmd, cwd=out, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(r.stderr)
@@ -77,37 +82,70 @@ def parse_asm(text):
     return kernels
 
 
-def verdict(old, new):
+def verdict(old, new, hot_re):
     if old == new:
         return "identical"
     mask = lambda blocks: [[REG.sub("r", i) for i in blk] for blk in blocks]          # noqa: E731
     if mask(old) == mask(new):
         return "registers"
-    hot = lambda blocks: [[i.split()[0] for i in blk] for blk in blocks if any(HOT.search(i) for i in blk)]      # noqa: E731
+    hot = lambda blocks: [[i.split()[0] for i in blk] for blk in blocks if any(hot_re.search(i) for i in blk)]      # noqa: E731
     ho, hn = hot(old), hot(new)
     if ho == hn:
         return "outside"
-    bag = lambda blocks: sorted(INVERSE.get(op, op) for blk in blocks for op in blk)          # noqa: E731
-    return "order" if bag(ho) == bag(hn) else f"HOT LOOP {sum(map(len, ho))} -> {sum(map(len, hn))}"
+    bag = lambda blocks: collections.Counter(INVERSE.get(op, op) for blk in blocks for op in blk)          # noqa: E731
+    if bag(ho) == bag(hn):
+        return "order"
+    delta = [f"-{n} {op}" for op, n in sorted((bag(ho) - bag(hn)).items())] + [f"+{n} {op}" for op, n in sorted((bag(hn) - bag(ho)).items())]
+    return f"HOT LOOP {sum(map(len, ho))} -> {sum(map(len, hn))} ({', '.join(delta)})"
+
+
+TYPES = (("DF16_", "_Float16"), ("f", "float"), ("i", "int"), ("b", "bool"))
 
 
 def demangle(names):
-    """_ZN6chatts16gemv_ldsx_kernelILi2ELi2ELi0ELb1EEEvNS_10GemvParamsE -> gemv_ldsx_kernel<2, 2, 0, true> (integer and bool arguments only)"""
+    """_ZN6chatts16gemv_ldsx_kernelILi2ELi2ELi0ELb1EEEvNS_10GemvParamsE -> gemv_ldsx_kernel<2, 2, 0, true>: the kernel's name in
+    namespace chatts and its template arguments (integer and bool literals, float / _Float16 / int / bool types); a name of another
+    shape stays as it is"""
     out = {}
     for n in names:
-        m = re.match(r"_ZN6chatts\d+(\w+?_kernel)I((?:L[ib]\d+E)+)EEvNS_10GemvParamsE$", n)
-        args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2))]
-        out[n] = f"{m.group(1)}<{', '.join(args)}>"
+        out[n] = n
+        m = re.match(r"_ZN6chatts(\d+)", n)
+        if not m:
+            continue
+        at = m.end() + int(m.group(1))
+        name, rest, args = n[m.end():at], n[at:], []
+        if rest.startswith("I"):
+            rest = rest[1:]
+            while rest and not rest.startswith("E"):
+                lit = re.match(r"L([ib])(\d+)E", rest)
+                typ = next((t for t in TYPES if rest.startswith(t[0])), None)
+                if lit:
+                    args.append(("true" if lit.group(2) == "1" else "false") if lit.group(1) == "b" else lit.group(2))
+                    rest = rest[lit.end():]
+                elif typ:
+                    args.append(typ[1])
+                    rest = rest[len(typ[0]):]
+                else:
+                    break
+            if not rest.startswith("E"):
+                continue
+        out[n] = name + (f"<{', '.join(args)}>" if args else "")
     return out
 
 
 def main():
-    old_src = sys.argv[1]
-    new_src = sys.argv[2] if len(sys.argv) > 2 else os.path.join(b.CSRC, "gemv.hip")
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--source", default="gemv.hip", help="the file of csrc/ that NEW defaults to")
+    ap.add_argument("--hot", default=GEMV_HOT, help="regular expression: a basic block with a match is a hot block")
+    ap.add_argument("old")
+    ap.add_argument("new", nargs="?")
+    args = ap.parse_args()
+    new_src = args.new or os.path.join(b.CSRC, args.source)
+    hot_re = re.compile(args.hot)
     with tempfile.TemporaryDirectory() as tmp:
-        (ro, ao), (rn, an) = compile_one(old_src, os.path.join(tmp, "old")), compile_one(new_src, os.path.join(tmp, "new"))
+        (ro, ao), (rn, an) = compile_one(args.old, os.path.join(tmp, "old")), compile_one(new_src, os.path.join(tmp, "new"))
     names = demangle(sorted(set(ro) | set(rn)))
-    print("compiled for gfx950 with " + " ".join(b.FLAGS) + "; nothing in this table was run")
+    print("compiled for gfx950 with " + " ".join(b.FLAGS) + f"; hot blocks: /{args.hot}/; nothing in this table was run")
     print(f"{'kernel':58s} {'VGPRs':>10s} {'SGPRs':>10s} {'scratch':>8s} {'occ':>8s}  stream")
     counts, worse = {}, []
     for mangled, name in sorted(names.items(), key=lambda kv: kv[1]):
@@ -116,11 +154,11 @@ def main():
             v = "only in the old file" if n is None else "only in the new file"
             cols = [(o or n)[key] + ("    -" if n is None else "") for _, key in FIELDS]
         else:
-            v = verdict(ao[mangled], an[mangled])
+            v = verdict(ao[mangled], an[mangled], hot_re)
             cols = [f"{o[key]} -> {n[key]}" if o[key] != n[key] else o[key] for _, key in FIELDS]
             if int(n["ScratchSize [bytes/lane]"]) > int(o["ScratchSize [bytes/lane]"]) or int(n["Occupancy [waves/SIMD]"]) < int(o["Occupancy [waves/SIMD]"]):
                 worse.append(name)
-        kind = re.sub(r" \d+ -> \d+$", "", v)
+        kind = "HOT LOOP" if v.startswith("HOT LOOP") else v
         counts[kind] = counts.get(kind, 0) + 1
         print(f"{name:58s} {cols[0]:>10s} {cols[1]:>10s} {cols[2]:>8s} {cols[3]:>8s}  {v}")
     print("summary: " + ", ".join(f"{k}: {v}" for k, v in sorted(counts.items())))
