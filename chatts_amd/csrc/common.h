@@ -110,6 +110,22 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
   return t;
 }
 
+// a guarded 16-byte load: 4 floats, or zeros (a select, not a branch around the load)
+__device__ __forceinline__ f32x4 load4_if(bool on, const float* p) { return on ? *reinterpret_cast<const f32x4*>(p) : (f32x4){0.f, 0.f, 0.f, 0.f}; }
+
+// The RMSNorm arithmetic (Qwen2RMSNorm: sum of squares in float32, y = w * (x * rstd)) of every kernel that forms one.  ONE definition each
+// = one contraction pattern and one association everywhere: the fused forms are bit-identical to the stand-alone kernels because of it.
+__device__ __forceinline__ float sumsq4(float ss, const f32x4 v) {      // one partial-sum step
+  ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+  return ss;
+}
+__device__ __forceinline__ float rms_rstd(float ss, float* red, int n, float eps) {      // 256 threads' partial sums -> the row's rstd
+  return rsqrtf(block_sum<4>(ss, red) / (float)n + eps);
+}
+__device__ __forceinline__ void norm4(const f32x4 v, const f32x4 g, float rstd, float (&o)[4]) {
+  o[0] = g.x * (v.x * rstd); o[1] = g.y * (v.y * rstd); o[2] = g.z * (v.z * rstd); o[3] = g.w * (v.w * rstd);
+}
+
 // ---- KV cache addressing ------------------------------------------------------------------------------------------------
 // Contiguous form: one sequence's layer cache is [n_kv, max_ctx, 128].  Block-paged form (table != nullptr,
 // ChattsKvCache.block_table): the layer's pool is [n_blocks, n_kv, 2^log_block, 128] and logical key j of the sequence lives

@@ -1,6 +1,6 @@
 // elementwise.hip - the small HBM/L2-bound kernels around the projections:
 // RMSNorm, RoPE + KV-cache write, embedding gather + TS merge, argmax, residual add.
-#include "common.h"
+#include "gemm_common.h"
 
 namespace chatts {
 
@@ -16,34 +16,15 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
   const float* xr = x + (size_t)blockIdx.x * ldx;
   float* yr = PLANES ? nullptr : y + (size_t)blockIdx.x * hidden;
   float ss = 0.f;
+  for (int k = threadIdx.x * 4; k < hidden; k += 1024) ss = sumsq4(ss, *reinterpret_cast<const f32x4*>(xr + k));
+  const float rstd = rms_rstd(ss, red, hidden, eps);
   for (int k = threadIdx.x * 4; k < hidden; k += 1024) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + k);
-    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
-  ss = block_sum<4>(ss, red);
-  const float rstd = rsqrtf(ss / (float)hidden + eps);
-  for (int k = threadIdx.x * 4; k < hidden; k += 1024) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + k);
-    const f32x4 g = *reinterpret_cast<const f32x4*>(w + k);
-    f32x4 o;
-    o.x = g.x * (v.x * rstd); o.y = g.y * (v.y * rstd); o.z = g.z * (v.z * rstd); o.w = g.w * (v.w * rstd);
-    if (PLANES) {
-      // no contraction: o is a product, and folding it into the subtraction as an FMA would make lo differ from the split of
-      // the ROUNDED float32 value that the float32 variant stores
-#pragma clang fp contract(off)
-      typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-      bf16x4_t hv, lv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)o[j];
-        hv[j] = h;
-        lv[j] = (__bf16)(o[j] - (float)h);
-      }
-      *reinterpret_cast<bf16x4_t*>(hi + (size_t)blockIdx.x * ldp + k) = hv;
-      *reinterpret_cast<bf16x4_t*>(lo + (size_t)blockIdx.x * ldp + k) = lv;
-    } else {
-      *reinterpret_cast<f32x4*>(yr + k) = o;
-    }
+    float o[4];
+    norm4(*reinterpret_cast<const f32x4*>(xr + k), *reinterpret_cast<const f32x4*>(w + k), rstd, o);
+    // (the planes are the split of the ROUNDED float32 value that the float32 variant stores: store_planes4 keeps the product o out of
+    // its subtraction)
+    if (PLANES) store_planes4(hi, lo, (size_t)blockIdx.x * ldp, k, o);
+    else *reinterpret_cast<f32x4*>(yr + k) = (f32x4){o[0], o[1], o[2], o[3]};
   }
 }
 

@@ -24,7 +24,7 @@
 #include <string.h>
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "splitk_epilogue.h"
 
 namespace chatts {
 
@@ -466,89 +466,58 @@ int launch_split_bf16x2(const float* x, int m, int k, int ldx, uint16_t* hi, uin
 }
 
 // Sum split-K partials in a fixed order and apply the epilogue.  One thread per output element.
-__global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __restrict__ ws, int sk, int m, int n,
-                                                             const float* __restrict__ bias,
-                                                             const float* __restrict__ resid, float* __restrict__ c,
-                                                             int ldc, int epilogue, const float* __restrict__ scale,
-                                                             uint16_t* __restrict__ c_hi, uint16_t* __restrict__ c_lo, int ldcp) {
-  const int ncols = epilogue == CHATTS_EPI_SWIGLU ? n / 2 : n;
+__global__ __launch_bounds__(256) void splitk_epilogue_kernel(SplitkEpi e) {
+  const int n = e.n, ncols = e.epilogue == CHATTS_EPI_SWIGLU ? n / 2 : n;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (size_t)m * ncols) return;
+  if (idx >= (size_t)e.m * ncols) return;
   const int row = (int)(idx / ncols), col = (int)(idx % ncols);
-  const size_t plane = (size_t)m * n;
-  if (epilogue == CHATTS_EPI_SWIGLU) {
+  const size_t plane = (size_t)e.m * n;
+  float v = 0.f;
+  if (e.epilogue == CHATTS_EPI_SWIGLU) {
     const int prow = (col >> 4) * 32 + (col & 15);
     float g = 0.f, u = 0.f;
-    for (int s = 0; s < sk; ++s) {
-      g += ws[s * plane + (size_t)row * n + prow];
-      u += ws[s * plane + (size_t)row * n + prow + 16];
+    for (int s = 0; s < e.sk; ++s) {
+      g += e.ws[s * plane + (size_t)row * n + prow];
+      u += e.ws[s * plane + (size_t)row * n + prow + 16];
     }
-    if (scale) { g *= scale[prow]; u *= scale[prow + 16]; }
-    if (bias) { g += bias[prow]; u += bias[prow + 16]; }
-    if (c_hi) store_planes(c_hi, c_lo, (size_t)row * ldcp + col, silu_g(g) * u);
-    else c[(size_t)row * ldc + col] = silu_g(g) * u;
-    return;
+    if (e.scale) { g *= e.scale[prow]; u *= e.scale[prow + 16]; }
+    if (e.bias) { g += e.bias[prow]; u += e.bias[prow + 16]; }
+    v = silu_g(g) * u;
+  } else {
+    for (int s = 0; s < e.sk; ++s) v += e.ws[s * plane + (size_t)row * n + col];
+    if (e.scale) v *= e.scale[col];
+    if (e.bias) v += e.bias[col];
+    if (e.epilogue == CHATTS_EPI_GELU) v = gelu_erf_f(v);
+    if (e.epilogue == CHATTS_EPI_RESID) v = e.resid[(size_t)row * e.ldc + col] + v;
   }
-  float v = 0.f;
-  for (int s = 0; s < sk; ++s) v += ws[s * plane + (size_t)row * n + col];
-  if (scale) v *= scale[col];
-  if (bias) v += bias[col];
-  if (epilogue == CHATTS_EPI_GELU) v = gelu_erf_f(v);
-  if (epilogue == CHATTS_EPI_RESID) v = resid[(size_t)row * ldc + col] + v;
-  if (c_hi) store_planes(c_hi, c_lo, (size_t)row * ldcp + col, v);
-  else c[(size_t)row * ldc + col] = v;
+  if (e.hi) store_planes(e.hi, e.lo, (size_t)row * e.ldp + col, v);
+  else e.c[(size_t)row * e.ldc + col] = v;
 }
 
 // The same epilogue, four columns per thread (N % 4 == 0, sk <= 8, no SwiGLU pairing, no stream-K): 16-byte loads instead of 4-byte
 // ones and all slabs of a thread requested at once.  Same sums in the same order per element: bit-identical to the kernel above.
-__global__ __launch_bounds__(256) void splitk_epilogue_v4_kernel(const float* __restrict__ ws, int sk, int m, int n,
-                                                                const float* __restrict__ bias, const float* __restrict__ resid,
-                                                                float* __restrict__ c, int ldc, int epilogue,
-                                                                const float* __restrict__ scale, uint16_t* __restrict__ c_hi,
-                                                                uint16_t* __restrict__ c_lo, int ldcp) {
-  const int n4 = n >> 2;
+__global__ __launch_bounds__(256) void splitk_epilogue_v4_kernel(SplitkEpi e) {
+  const int n4 = e.n >> 2;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (size_t)m * n4) return;
+  if (idx >= (size_t)e.m * n4) return;
   const int row = (int)(idx / n4), col = (int)(idx % n4) * 4;
-  const size_t plane = (size_t)m * n, at = (size_t)row * n + col;
   f32x4 t8[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) t8[s] = *reinterpret_cast<const f32x4*>(ws + (s < sk ? s : sk - 1) * plane + at);
-  f32x4 r4 = {0.f, 0.f, 0.f, 0.f}, s4 = r4, b4 = r4;            // residual, scale, bias: requested with the slabs (one round trip)
-  if (epilogue == CHATTS_EPI_RESID) r4 = *reinterpret_cast<const f32x4*>(resid + (size_t)row * ldc + col);
-  if (scale) s4 = *reinterpret_cast<const f32x4*>(scale + col);
-  if (bias) b4 = *reinterpret_cast<const f32x4*>(bias + col);
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 8; ++s)
-    if (s < sk) { v[0] += t8[s].x; v[1] += t8[s].y; v[2] += t8[s].z; v[3] += t8[s].w; }
-  const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, sc[4] = {s4.x, s4.y, s4.z, s4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (scale) v[j] *= sc[j];
-    if (bias) v[j] += bb[j];
-    if (epilogue == CHATTS_EPI_GELU) v[j] = gelu_erf_f(v[j]);
-    if (epilogue == CHATTS_EPI_RESID) v[j] = rr[j] + v[j];
-  }
-  if (c_hi) {
-    if ((ldcp & 3) == 0) {      // both planes as one 8-byte store each (store_planes' arithmetic)
-#pragma clang fp contract(off)
-      typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-      bf16x4_t hv, lv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        hv[j] = h;
-        lv[j] = (__bf16)(v[j] - (float)h);
-      }
-      *reinterpret_cast<bf16x4_t*>(c_hi + (size_t)row * ldcp + col) = hv;
-      *reinterpret_cast<bf16x4_t*>(c_lo + (size_t)row * ldcp + col) = lv;
+  slab_load<8>(e.ws, e.sk, (size_t)e.m * e.n, (size_t)row * e.n + col, t8);
+  f32x4 r4 = {0.f, 0.f, 0.f, 0.f}, s4 = r4, b4 = r4;            // residual, scale, bias: requested with the slabs (one round trip);
+  if (e.epilogue == CHATTS_EPI_RESID) r4 = *reinterpret_cast<const f32x4*>(e.resid + (size_t)row * e.ldc + col);      // branches, not
+  if (e.scale) s4 = *reinterpret_cast<const f32x4*>(e.scale + col);                                                    // load4_if: the
+  if (e.bias) b4 = *reinterpret_cast<const f32x4*>(e.bias + col);                                                      // selects cost 2 VGPRs
+  const f32x4 v = epi_finish4<true>(slab_sum<8>(t8, e.sk), s4, b4, r4, e.scale, e.bias, e.epilogue);
+  if (e.hi) {
+    const float o[4] = {v.x, v.y, v.z, v.w};
+    if ((e.ldp & 3) == 0) {
+      store_planes4(e.hi, e.lo, (size_t)row * e.ldp, col, o);
     } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) store_planes(c_hi, c_lo, (size_t)row * ldcp + col + j, v[j]);
+      for (int j = 0; j < 4; ++j) store_planes(e.hi, e.lo, (size_t)row * e.ldp + col + j, o[j]);
     }
   } else {
-    *reinterpret_cast<f32x4*>(c + (size_t)row * ldc + col) = (f32x4){v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(e.c + (size_t)row * e.ldc + col) = v;
   }
 }
 
@@ -556,130 +525,46 @@ __global__ __launch_bounds__(256) void splitk_epilogue_v4_kernel(const float* __
 // (fixed order), applies bias / residual, writes the row, and - the row's sum of squares being at hand - writes
 // norm_w * (row * rsqrt(mean(row^2) + eps)) as bf16 hi / lo planes, the next projection's operand.  Replaces the
 // element-wise epilogue launch and the rmsnorm_planes launch behind it (same arithmetic, same order: bit-identical).
-__global__ __launch_bounds__(256) void splitk_epilogue_norm_kernel(const float* __restrict__ ws, int sk, int m, int n,
-                                                                  const float* __restrict__ bias, const float* __restrict__ resid,
-                                                                  float* __restrict__ c, int ldc, int epilogue,
-                                                                  const float* __restrict__ scale, const float* __restrict__ norm_w,
-                                                                  float eps, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                                  int ldp) {
+__global__ __launch_bounds__(256) void splitk_epilogue_norm_kernel(SplitkEpi e) {
   __shared__ float red[4];
-  const int row = blockIdx.x;
-  const size_t plane = (size_t)m * n;
+  const int row = blockIdx.x, n = e.n;
+  const size_t plane = (size_t)e.m * n;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   float ss = 0.f;
   for (int col = threadIdx.x * 4; col < n; col += 1024) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (sk <= 4) {          // the usual split counts: all slabs requested at once, summed in split order (same sums, one round trip)
+    f32x4 v = zero;
+    if (e.sk <= 4) {        // the usual split counts: all slabs requested at once, summed in split order (same sums, one round trip)
       f32x4 t4[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) t4[s] = *reinterpret_cast<const f32x4*>(ws + (s < sk ? s : sk - 1) * plane + (size_t)row * n + col);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        if (s < sk) { v.x += t4[s].x; v.y += t4[s].y; v.z += t4[s].z; v.w += t4[s].w; }
+      slab_load<4>(e.ws + (size_t)row * n, e.sk, plane, col, t4);
+      v = slab_sum<4>(t4, e.sk);
     } else {
-      for (int s = 0; s < sk; ++s) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(ws + s * plane + (size_t)row * n + col);
+      for (int s = 0; s < e.sk; ++s) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(e.ws + s * plane + (size_t)row * n + col);
         v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
       }
     }
-    if (scale) { const f32x4 t = *reinterpret_cast<const f32x4*>(scale + col); v.x *= t.x; v.y *= t.y; v.z *= t.z; v.w *= t.w; }
-    if (bias) { const f32x4 t = *reinterpret_cast<const f32x4*>(bias + col); v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
-    if (epilogue == CHATTS_EPI_RESID) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(resid + (size_t)row * ldc + col);
-      v.x = t.x + v.x; v.y = t.y + v.y; v.z = t.z + v.z; v.w = t.w + v.w;
-    }
-    *reinterpret_cast<f32x4*>(c + (size_t)row * ldc + col) = v;
-    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;        // same accumulation pattern as rmsnorm_kernel
+    v = epi_finish4<false>(v, load4_if(e.scale, e.scale + col), load4_if(e.bias, e.bias + col),
+                           load4_if(e.epilogue == CHATTS_EPI_RESID, e.resid + (size_t)row * e.ldc + col), e.scale, e.bias, e.epilogue);
+    *reinterpret_cast<f32x4*>(e.c + (size_t)row * e.ldc + col) = v;
+    ss = sumsq4(ss, v);
   }
-  ss = block_sum<4>(ss, red);
-  const float rstd = rsqrtf(ss / (float)n + eps);
+  const float rstd = rms_rstd(ss, red, n, e.eps);
   for (int col = threadIdx.x * 4; col < n; col += 1024) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(c + (size_t)row * ldc + col);    // this thread's own stores
-    const f32x4 g = *reinterpret_cast<const f32x4*>(norm_w + col);
-    const float o[4] = {g.x * (v.x * rstd), g.y * (v.y * rstd), g.z * (v.z * rstd), g.w * (v.w * rstd)};
-    {
-#pragma clang fp contract(off)   // lo must be the split of the ROUNDED product, as in rmsnorm_kernel<true>
-      typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-      bf16x4_t hv, lv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)o[j];
-        hv[j] = h;
-        lv[j] = (__bf16)(o[j] - (float)h);
-      }
-      *reinterpret_cast<bf16x4_t*>(hi + (size_t)row * ldp + col) = hv;
-      *reinterpret_cast<bf16x4_t*>(lo + (size_t)row * ldp + col) = lv;
-    }
+    float o[4];      // (from this thread's own stores)
+    norm4(*reinterpret_cast<const f32x4*>(e.c + (size_t)row * e.ldc + col), *reinterpret_cast<const f32x4*>(e.norm_w + col), rstd, o);
+    store_planes4(e.hi, e.lo, (size_t)row * e.ldp, col, o);
   }
 }
 
-// The same kernel with every memory round trip of a thread taken ONCE (round 5): sk <= 4 slabs, rows of <= 1024 kIt columns.  The kernel
-// above walks a row in kIt dependent iterations - slab loads, wait, store - and then re-reads its own stores for the planes: ~2 kIt round
-// trips per workgroup, 16.5 us per 798 x 5120 epilogue (two per layer in a prefill chunk).  Here a thread requests all slabs, the residual,
-// bias and norm weights of all its kIt column groups up front, keeps the row values in registers, and writes c and the planes from them.
+// The same kernel with every memory round trip of a thread taken ONCE (round 5; the row body is splitk_epilogue.h's): sk <= 4 slabs, rows
+// of <= 1024 kIt columns.  The kernel above walks a row in kIt dependent iterations - slab loads, wait, store - and then re-reads its own
+// stores for the planes: ~2 kIt round trips per workgroup, 16.5 us per 798 x 5120 epilogue (two per layer in a prefill chunk).
 // Same sums in the same order (split order per element, the row's sum of squares in column-group order per thread): bit-identical.
 template <int kIt>
-__global__ __launch_bounds__(256) void splitk_epilogue_norm_reg_kernel(const float* __restrict__ ws, int sk, int m, int n,
-                                                                      const float* __restrict__ bias, const float* __restrict__ resid,
-                                                                      float* __restrict__ c, int ldc, int epilogue,
-                                                                      const float* __restrict__ scale, const float* __restrict__ norm_w,
-                                                                      float eps, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, int ldp) {
+__global__ __launch_bounds__(256) void splitk_epilogue_norm_reg_kernel(SplitkEpi e) {
   __shared__ float red[4];
   const int row = blockIdx.x;
-  const size_t plane = (size_t)m * n;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4 t[kIt][4], rs[kIt], gw[kIt], sc4[kIt], b4[kIt];
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int col = threadIdx.x * 4 + it * 1024;
-    const bool live = col < n;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-      t[it][s] = live ? *reinterpret_cast<const f32x4*>(ws + (s < sk ? s : sk - 1) * plane + (size_t)row * n + col) : zero;
-    rs[it] = (live && epilogue == CHATTS_EPI_RESID) ? *reinterpret_cast<const f32x4*>(resid + (size_t)row * ldc + col) : zero;
-    gw[it] = live ? *reinterpret_cast<const f32x4*>(norm_w + col) : zero;
-    sc4[it] = (live && scale) ? *reinterpret_cast<const f32x4*>(scale + col) : zero;
-    b4[it] = (live && bias) ? *reinterpret_cast<const f32x4*>(bias + col) : zero;
-  }
-  f32x4 keep[kIt];
-  float ss = 0.f;
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int col = threadIdx.x * 4 + it * 1024;
-    f32x4 v = zero;
-    if (col < n) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        if (s < sk) { v.x += t[it][s].x; v.y += t[it][s].y; v.z += t[it][s].z; v.w += t[it][s].w; }
-      if (scale) { v.x *= sc4[it].x; v.y *= sc4[it].y; v.z *= sc4[it].z; v.w *= sc4[it].w; }
-      if (bias) { v.x += b4[it].x; v.y += b4[it].y; v.z += b4[it].z; v.w += b4[it].w; }
-      if (epilogue == CHATTS_EPI_RESID) { v.x = rs[it].x + v.x; v.y = rs[it].y + v.y; v.z = rs[it].z + v.z; v.w = rs[it].w + v.w; }
-      *reinterpret_cast<f32x4*>(c + (size_t)row * ldc + col) = v;
-      ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;        // same accumulation pattern as rmsnorm_kernel
-    }
-    keep[it] = v;
-  }
-  ss = block_sum<4>(ss, red);
-  const float rstd = rsqrtf(ss / (float)n + eps);
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int col = threadIdx.x * 4 + it * 1024;
-    if (col >= n) continue;
-    const f32x4 v = keep[it], g = gw[it];
-    const float o[4] = {g.x * (v.x * rstd), g.y * (v.y * rstd), g.z * (v.z * rstd), g.w * (v.w * rstd)};
-    {
-#pragma clang fp contract(off)   // lo must be the split of the ROUNDED product, as in rmsnorm_kernel<true>
-      typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-      bf16x4_t hv, lv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)o[j];
-        hv[j] = h;
-        lv[j] = (__bf16)(o[j] - (float)h);
-      }
-      *reinterpret_cast<bf16x4_t*>(hi + (size_t)row * ldp + col) = hv;
-      *reinterpret_cast<bf16x4_t*>(lo + (size_t)row * ldp + col) = lv;
-    }
-  }
+  splitk_epilogue_reg_row<kIt, false>(e, row, red, [&](int col, const float (&o)[4], bool) { store_planes4(e.hi, e.lo, (size_t)row * e.ldp, col, o); });
 }
 
 // The same kernel for FEW rows (batched decode, M <= 16): one workgroup per row leaves the chip idle (16 workgroups), so gridDim.y = Q
@@ -688,16 +573,11 @@ __global__ __launch_bounds__(256) void splitk_epilogue_norm_reg_kernel(const flo
 // re-read of the slabs by Q workgroups is L2 traffic (Q x sk x M x N x 4 bytes: 16 MB at Q = 8, sk = 6, 16 x 5120).  Because a
 // workgroup reads resid columns that another one updates, c must NOT alias resid here (the batched decoder ping-pongs x / xn).
 template <int kMaxIt, int kG>
-__global__ __launch_bounds__(256) void splitk_epilogue_norm_q_kernel(const float* __restrict__ ws, int sk, int m, int n,
-                                                                    const float* __restrict__ bias, const float* __restrict__ resid,
-                                                                    float* __restrict__ c, int ldc, int epilogue,
-                                                                    const float* __restrict__ scale, const float* __restrict__ norm_w,
-                                                                    float eps, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                                    int ldp) {
+__global__ __launch_bounds__(256) void splitk_epilogue_norm_q_kernel(SplitkEpi e) {
   __shared__ float red[4];
-  const int row = blockIdx.x;
+  const int row = blockIdx.x, n = e.n;
   const bool mine = (int)(threadIdx.x * gridDim.y / 256) == (int)blockIdx.y;
-  const size_t plane = (size_t)m * n;
+  const size_t plane = (size_t)e.m * n;
   f32x4 keep[kMaxIt];
   float ss = 0.f;
   // Column groups are taken kG at a time (kG = 3 since round 5, option EPI_NORM_Q_GROUPS; 1 = the round-3 walk): all slabs (sk <= 8;
@@ -720,12 +600,10 @@ __global__ __launch_bounds__(256) void splitk_epilogue_norm_q_kernel(const float
       const int it = g0 + u;
       const int col = threadIdx.x * 4 + it * 1024;
       const int cc = (it < kMaxIt && col < n) ? col : 0;
-#pragma unroll
-      for (int s = 0; s < 8; ++s)
-        t8[u][s] = *reinterpret_cast<const f32x4*>(ws + (s < sk ? s : sk - 1) * plane + (size_t)row * n + cc);
-      tr[u] = epilogue == CHATTS_EPI_RESID ? *reinterpret_cast<const f32x4*>(resid + (size_t)row * ldc + cc) : zero;
-      tsc[u] = scale ? *reinterpret_cast<const f32x4*>(scale + cc) : zero;
-      tb[u] = bias ? *reinterpret_cast<const f32x4*>(bias + cc) : zero;
+      slab_load<8>(e.ws + (size_t)row * n, e.sk, plane, cc, t8[u]);
+      tr[u] = load4_if(e.epilogue == CHATTS_EPI_RESID, e.resid + (size_t)row * e.ldc + cc);
+      tsc[u] = load4_if(e.scale, e.scale + cc);
+      tb[u] = load4_if(e.bias, e.bias + cc);
     }
 #pragma unroll
     for (int u = 0; u < kG; ++u) {
@@ -734,14 +612,15 @@ __global__ __launch_bounds__(256) void splitk_epilogue_norm_q_kernel(const float
       const int col = threadIdx.x * 4 + it * 1024;
       f32x4 v = zero;
       if (col < n) {
+        // (written out, not slab_sum + epi_finish4: through them <8, 1> contracted its sum of squares into FMAs - other bits of rstd)
 #pragma unroll
         for (int s = 0; s < 8; ++s)
-          if (s < sk) { v.x += t8[u][s].x; v.y += t8[u][s].y; v.z += t8[u][s].z; v.w += t8[u][s].w; }
-        if (scale) { v.x *= tsc[u].x; v.y *= tsc[u].y; v.z *= tsc[u].z; v.w *= tsc[u].w; }
-        if (bias) { v.x += tb[u].x; v.y += tb[u].y; v.z += tb[u].z; v.w += tb[u].w; }
-        if (epilogue == CHATTS_EPI_RESID) { v.x = tr[u].x + v.x; v.y = tr[u].y + v.y; v.z = tr[u].z + v.z; v.w = tr[u].w + v.w; }
-        if (mine) *reinterpret_cast<f32x4*>(c + (size_t)row * ldc + col) = v;
-        ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;        // same accumulation pattern as rmsnorm_kernel
+          if (s < e.sk) { v.x += t8[u][s].x; v.y += t8[u][s].y; v.z += t8[u][s].z; v.w += t8[u][s].w; }
+        if (e.scale) { v.x *= tsc[u].x; v.y *= tsc[u].y; v.z *= tsc[u].z; v.w *= tsc[u].w; }
+        if (e.bias) { v.x += tb[u].x; v.y += tb[u].y; v.z += tb[u].z; v.w += tb[u].w; }
+        if (e.epilogue == CHATTS_EPI_RESID) { v.x = tr[u].x + v.x; v.y = tr[u].y + v.y; v.z = tr[u].z + v.z; v.w = tr[u].w + v.w; }
+        if (mine) *reinterpret_cast<f32x4*>(e.c + (size_t)row * e.ldc + col) = v;
+        ss = sumsq4(ss, v);
       }
       keep[it] = v;
     }
@@ -750,31 +629,17 @@ __global__ __launch_bounds__(256) void splitk_epilogue_norm_q_kernel(const float
 #pragma unroll
   for (int it = 0; it < kMaxIt; ++it) {
     const int col = threadIdx.x * 4 + it * 1024;
-    gw[it] = (kG > 1 && mine && col < n) ? *reinterpret_cast<const f32x4*>(norm_w + col) : zero;
+    gw[it] = load4_if(kG > 1 && mine && col < n, e.norm_w + col);
   }
-  ss = block_sum<4>(ss, red);
-  const float rstd = rsqrtf(ss / (float)n + eps);
+  const float rstd = rms_rstd(ss, red, n, e.eps);
   if (!mine) return;
 #pragma unroll
   for (int it = 0; it < kMaxIt; ++it) {
     const int col = threadIdx.x * 4 + it * 1024;
     if (col >= n) continue;
-    const f32x4 v = keep[it];
-    const f32x4 g = kG > 1 ? gw[it] : *reinterpret_cast<const f32x4*>(norm_w + col);
-    const float o[4] = {g.x * (v.x * rstd), g.y * (v.y * rstd), g.z * (v.z * rstd), g.w * (v.w * rstd)};
-    {
-#pragma clang fp contract(off)   // lo must be the split of the ROUNDED product, as in rmsnorm_kernel<true>
-      typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-      bf16x4_t hv, lv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)o[j];
-        hv[j] = h;
-        lv[j] = (__bf16)(o[j] - (float)h);
-      }
-      *reinterpret_cast<bf16x4_t*>(hi + (size_t)row * ldp + col) = hv;
-      *reinterpret_cast<bf16x4_t*>(lo + (size_t)row * ldp + col) = lv;
-    }
+    float o[4];
+    norm4(keep[it], kG > 1 ? gw[it] : *reinterpret_cast<const f32x4*>(e.norm_w + col), rstd, o);
+    store_planes4(e.hi, e.lo, (size_t)row * e.ldp, col, o);
   }
 }
 
@@ -923,6 +788,57 @@ size_t gemm_workspace(int m, int n, int k) {
   return sk > 1 ? (size_t)sk * m * n * sizeof(float) : 0;
 }
 
+// What follows a GEMM launch: the epilogue of a split (sk > 1; the first form that takes the call, in this order), and the consumer's RMSNorm.
+static int launch_splitk_epilogue(const ChattsLinearArgs* a, int sk, const RopeFuse* rope, bool* rope_done, hipStream_t s) {
+  const bool post_norm = a->post_norm_w != nullptr;
+  SplitkEpi e{reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->resid, a->c, a->ldc, a->epilogue,
+              a->w8 ? a->w8_scale : nullptr, a->post_norm_w, a->post_norm_eps, a->post_hi, a->post_lo, a->ld_post};
+  if (sk > 1 && post_norm) {        // epilogue + the consumer's RMSNorm in one row-wise launch
+    const int qsplit = opt_get(OPT_EPI_NORM_Q, 8), its = (a->n + 1023) / 1024;
+    if (a->m <= 16 && qsplit > 1 && qsplit <= 256 && sk <= 8 && a->n <= 8192 && a->n % 4 == 0 &&
+        (a->epilogue != CHATTS_EPI_RESID || a->c != a->resid)) {          // few rows: Q workgroups per row (c must not alias resid)
+      if (opt_get(OPT_EPI_NORM_Q_GROUPS, 3) == 1) hipLaunchKernelGGL((splitk_epilogue_norm_q_kernel<8, 1>), dim3(a->m, qsplit), dim3(256), 0, s, e);
+      else hipLaunchKernelGGL((splitk_epilogue_norm_q_kernel<8, 3>), dim3(a->m, qsplit), dim3(256), 0, s, e);
+      CHATTS_CHECK_LAUNCH("splitk_epilogue_norm_q");
+    } else if (sk <= 4 && its <= 8 && opt_get(OPT_EPI_NORM_REG, 1) != 0) {      // all round trips of a thread at once (bit-identical; 13.5)
+      splitk_epilogue_its(its, [&](auto k) {
+        hipLaunchKernelGGL((splitk_epilogue_norm_reg_kernel<decltype(k)::value>), dim3(a->m), dim3(256), 0, s, e);
+      });
+      CHATTS_CHECK_LAUNCH("splitk_epilogue_norm_reg");
+    } else {
+      hipLaunchKernelGGL(splitk_epilogue_norm_kernel, dim3(a->m), dim3(256), 0, s, e);
+      CHATTS_CHECK_LAUNCH("splitk_epilogue_norm");
+    }
+    return CHATTS_OK;
+  }
+  if (sk > 1 && rope && rope_done && !post_norm && a->epilogue == CHATTS_EPI_NONE && !a->c_hi && !a->w8 &&
+      a->n == (rope->n_q + 2 * rope->n_kv) * kHeadDim) {
+    const int waves = a->m * (rope->n_q + 2 * rope->n_kv);
+    if (rope->kv_f16)
+      hipLaunchKernelGGL(splitk_epilogue_rope_kernel<_Float16>, dim3((waves + 3) / 4), dim3(256), 0, s, e.ws, sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
+    else
+      hipLaunchKernelGGL(splitk_epilogue_rope_kernel<float>, dim3((waves + 3) / 4), dim3(256), 0, s, e.ws, sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
+    CHATTS_CHECK_LAUNCH("splitk_epilogue_rope");
+    *rope_done = true;
+    return CHATTS_OK;
+  }
+  e.hi = a->c_hi; e.lo = a->c_lo; e.ldp = a->ld_cplanes;      // the element-wise pair: the OUTPUT as planes
+  if (sk > 1 && sk <= 8 && a->epilogue != CHATTS_EPI_SWIGLU && a->n % 4 == 0 && a->ldc % 4 == 0 &&
+      ((uintptr_t)a->c % 16) == 0 && ((uintptr_t)a->resid % 16) == 0 && ((uintptr_t)a->bias % 16) == 0 &&
+      (!a->w8 || ((uintptr_t)a->w8_scale % 16) == 0) && opt_get(OPT_EPI_V4, 1) != 0) {
+    const size_t total = (size_t)a->m * (a->n / 4);
+    hipLaunchKernelGGL(splitk_epilogue_v4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e);
+    CHATTS_CHECK_LAUNCH("splitk_epilogue_v4");
+  } else if (sk > 1) {
+    const size_t total = (size_t)a->m * (a->epilogue == CHATTS_EPI_SWIGLU ? a->n / 2 : a->n);
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e);
+    CHATTS_CHECK_LAUNCH("splitk_epilogue");
+  }
+  if (post_norm)                  // no split-K epilogue to fuse into: the contract still holds, as its own launch (rows of c ldc apart)
+    return launch_rmsnorm_planes(a->c, a->ldc, a->post_norm_w, a->post_hi, a->post_lo, a->ld_post, a->m, a->n, a->post_norm_eps, s);
+  return CHATTS_OK;
+}
+
 int launch_gemm(const ChattsLinearArgs* a_in, hipStream_t s, const RopeFuse* rope, bool* rope_done) {
   int bm, sk;
   ChattsLinearArgs a_copy;
@@ -1016,79 +932,7 @@ int launch_gemm(const ChattsLinearArgs* a_in, hipStream_t s, const RopeFuse* rop
     }
   }
   CHATTS_CHECK_LAUNCH("gemm_bf16x2");
-  const bool post_norm = a->post_norm_w != nullptr;
-  if (sk > 1 && post_norm) {        // epilogue + the consumer's RMSNorm in one row-wise launch
-    const int qsplit = opt_get(OPT_EPI_NORM_Q, 8);
-    if (a->m <= 16 && qsplit > 1 && qsplit <= 256 && sk <= 8 && a->n <= 8192 && a->n % 4 == 0 &&
-        (a->epilogue != CHATTS_EPI_RESID || a->c != a->resid)) {          // few rows: Q workgroups per row (c must not alias resid)
-      if (opt_get(OPT_EPI_NORM_Q_GROUPS, 3) == 1)
-        hipLaunchKernelGGL((splitk_epilogue_norm_q_kernel<8, 1>), dim3(a->m, qsplit), dim3(256), 0, s,
-                           reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->resid, a->c, a->ldc, a->epilogue,
-                           a->w8 ? a->w8_scale : nullptr, a->post_norm_w, a->post_norm_eps, a->post_hi, a->post_lo, a->ld_post);
-      else
-        hipLaunchKernelGGL((splitk_epilogue_norm_q_kernel<8, 3>), dim3(a->m, qsplit), dim3(256), 0, s,
-                           reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->resid, a->c, a->ldc, a->epilogue,
-                           a->w8 ? a->w8_scale : nullptr, a->post_norm_w, a->post_norm_eps, a->post_hi, a->post_lo, a->ld_post);
-      CHATTS_CHECK_LAUNCH("splitk_epilogue_norm_q");
-      return CHATTS_OK;
-    }
-    const float* ws_f = reinterpret_cast<const float*>(a->workspace);
-    const float* sc = a->w8 ? a->w8_scale : nullptr;
-    const int its = (a->n + 1023) / 1024;
-    if (sk <= 4 && its <= 8 && opt_get(OPT_EPI_NORM_REG, 1) != 0) {      // all round trips of a thread at once (bit-identical; 13.5)
-#define CHATTS_EPI_REG(K) hipLaunchKernelGGL((splitk_epilogue_norm_reg_kernel<K>), dim3(a->m), dim3(256), 0, s, ws_f, sk, a->m, a->n, a->bias, \
-                                             a->resid, a->c, a->ldc, a->epilogue, sc, a->post_norm_w, a->post_norm_eps, a->post_hi, a->post_lo, a->ld_post)
-      switch (its) {
-        case 1: CHATTS_EPI_REG(1); break;
-        case 2: CHATTS_EPI_REG(2); break;
-        case 3: CHATTS_EPI_REG(3); break;
-        case 4: CHATTS_EPI_REG(4); break;
-        case 5: CHATTS_EPI_REG(5); break;
-        case 6: CHATTS_EPI_REG(6); break;
-        default: CHATTS_EPI_REG(8); break;
-      }
-#undef CHATTS_EPI_REG
-      CHATTS_CHECK_LAUNCH("splitk_epilogue_norm_reg");
-      return CHATTS_OK;
-    }
-    hipLaunchKernelGGL(splitk_epilogue_norm_kernel, dim3(a->m), dim3(256), 0, s, ws_f, sk,
-                       a->m, a->n, a->bias, a->resid, a->c, a->ldc, a->epilogue, sc, a->post_norm_w,
-                       a->post_norm_eps, a->post_hi, a->post_lo, a->ld_post);
-    CHATTS_CHECK_LAUNCH("splitk_epilogue_norm");
-    return CHATTS_OK;
-  }
-  if (sk > 1 && rope && rope_done && !post_norm && a->epilogue == CHATTS_EPI_NONE && !a->c_hi && !a->w8 &&
-      a->n == (rope->n_q + 2 * rope->n_kv) * kHeadDim) {
-    const int waves = a->m * (rope->n_q + 2 * rope->n_kv);
-    if (rope->kv_f16)
-      hipLaunchKernelGGL(splitk_epilogue_rope_kernel<_Float16>, dim3((waves + 3) / 4), dim3(256), 0, s,
-                         reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
-    else
-      hipLaunchKernelGGL(splitk_epilogue_rope_kernel<float>, dim3((waves + 3) / 4), dim3(256), 0, s,
-                         reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->c, a->ldc, *rope);
-    CHATTS_CHECK_LAUNCH("splitk_epilogue_rope");
-    *rope_done = true;
-    return CHATTS_OK;
-  }
-  if (sk > 1 && sk <= 8 && a->epilogue != CHATTS_EPI_SWIGLU && a->n % 4 == 0 && a->ldc % 4 == 0 &&
-      ((uintptr_t)a->c % 16) == 0 && ((uintptr_t)a->resid % 16) == 0 && ((uintptr_t)a->bias % 16) == 0 &&
-      (!a->w8 || ((uintptr_t)a->w8_scale % 16) == 0) && opt_get(OPT_EPI_V4, 1) != 0) {
-    const size_t total = (size_t)a->m * (a->n / 4);
-    hipLaunchKernelGGL(splitk_epilogue_v4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->resid, a->c, a->ldc, a->epilogue,
-                       a->w8 ? a->w8_scale : nullptr, a->c_hi, a->c_lo, a->ld_cplanes);
-    CHATTS_CHECK_LAUNCH("splitk_epilogue_v4");
-  } else if (sk > 1) {
-    const int ncols = a->epilogue == CHATTS_EPI_SWIGLU ? a->n / 2 : a->n;
-    const size_t total = (size_t)a->m * ncols;
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->resid, a->c,
-                       a->ldc, a->epilogue, a->w8 ? a->w8_scale : nullptr, a->c_hi, a->c_lo, a->ld_cplanes);
-    CHATTS_CHECK_LAUNCH("splitk_epilogue");
-  }
-  if (post_norm)                  // no split-K epilogue to fuse into: the contract still holds, as its own launch (rows of c ldc apart)
-    return launch_rmsnorm_planes(a->c, a->ldc, a->post_norm_w, a->post_hi, a->post_lo, a->ld_post, a->m, a->n, a->post_norm_eps, s);
-  return CHATTS_OK;
+  return launch_splitk_epilogue(a, sk, rope, rope_done, s);
 }
 
 }  // namespace chatts

@@ -35,6 +35,22 @@ __device__ __forceinline__ void store_planes(uint16_t* hi, uint16_t* lo, size_t 
   hi[off] = __builtin_bit_cast(uint16_t, h);
   lo[off] = __builtin_bit_cast(uint16_t, l);
 }
+// four consecutive elements at row_off + col (both % 4 == 0, planes 8-byte aligned): the same split, one 8-byte store per plane.  The
+// pragma sits in here, as above, so that a product handed in (a normed row, SwiGLU) cannot be contracted into the subtraction at any call
+// site.  row_off (wave-uniform at most call sites) and the lane's col stay apart: a scalar base and a 32-bit offset per store.
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_planes4(uint16_t* hi, uint16_t* lo, size_t row_off, int col, const float (&v)[4]) {
+#pragma clang fp contract(off)
+  bf16x4_t hv, lv;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const __bf16 h = (__bf16)v[j];
+    hv[j] = h;
+    lv[j] = (__bf16)(v[j] - (float)h);
+  }
+  *reinterpret_cast<bf16x4_t*>(hi + row_off + col) = hv;
+  *reinterpret_cast<bf16x4_t*>(lo + row_off + col) = lv;
+}
 
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float silu_g(float x) { return x / (1.0f + expf(-x)); }

@@ -23,8 +23,8 @@
 #include <type_traits>
 
 #include "f16q.h"
-#include "gemm_common.h"
 #include "ring_store.h"
+#include "splitk_epilogue.h"
 
 namespace chatts {
 
@@ -587,71 +587,24 @@ __global__ __launch_bounds__(256) void rmsnorm_f16q_kernel(const float* __restri
   __shared__ float red[4];
   const float* xr = x + (size_t)blockIdx.x * ldx;
   float ss = 0.f;
-  for (int k = threadIdx.x * 4; k < hidden; k += 1024) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + k);
-    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
-  ss = block_sum<4>(ss, red);
-  const float rstd = rsqrtf(ss / (float)hidden + eps);
+  for (int k = threadIdx.x * 4; k < hidden; k += 1024) ss = sumsq4(ss, *reinterpret_cast<const f32x4*>(xr + k));
+  const float rstd = rms_rstd(ss, red, hidden, eps);
   for (int k0 = 0; k0 < hidden; k0 += 1024) {
     const int k = k0 + threadIdx.x * 4;
     const bool live = k < hidden;
-    const f32x4 v = live ? *reinterpret_cast<const f32x4*>(xr + k) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    const f32x4 g = live ? *reinterpret_cast<const f32x4*>(w + k) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float ov[4] = {g.x * (v.x * rstd), g.y * (v.y * rstd), g.z * (v.z * rstd), g.w * (v.w * rstd)};
+    float ov[4];
+    norm4(load4_if(live, xr + k), load4_if(live, w + k), rstd, ov);
     f16q_put4(o, blockIdx.x, k, ov, live);
   }
 }
 
-// Split-K epilogue of the residual projections (splitk_epilogue_norm_reg_kernel's arithmetic: slabs in split order, bias, residual, the
-// row's sum of squares in column-group order) with the RMSNorm that follows written as f16q planes; norm_w == null: no planes
+// Split-K epilogue of the residual projections: splitk_epilogue_norm_reg_kernel's row (splitk_epilogue.h) with the RMSNorm that follows
+// written as f16q planes; norm_w == null: no planes
 template <int kIt>
-__global__ __launch_bounds__(256) void splitk_epilogue_f16q_kernel(const float* __restrict__ ws, int sk, int m, int n, const float* __restrict__ bias,
-                                                                  const float* __restrict__ resid, float* __restrict__ c, int ldc, int epilogue,
-                                                                  const float* __restrict__ norm_w, float eps, F16qPlanes o) {
+__global__ __launch_bounds__(256) void splitk_epilogue_f16q_kernel(SplitkEpi e, F16qPlanes o) {
   __shared__ float red[4];
   const int row = blockIdx.x;
-  const size_t plane = (size_t)m * n;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4 t[kIt][4], rs[kIt], gw[kIt], b4[kIt];
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int col = threadIdx.x * 4 + it * 1024;
-    const bool live = col < n;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-      t[it][s] = live ? *reinterpret_cast<const f32x4*>(ws + (s < sk ? s : sk - 1) * plane + (size_t)row * n + col) : zero;
-    rs[it] = (live && epilogue == CHATTS_EPI_RESID) ? *reinterpret_cast<const f32x4*>(resid + (size_t)row * ldc + col) : zero;
-    gw[it] = (live && norm_w) ? *reinterpret_cast<const f32x4*>(norm_w + col) : zero;
-    b4[it] = (live && bias) ? *reinterpret_cast<const f32x4*>(bias + col) : zero;
-  }
-  f32x4 keep[kIt];
-  float ss = 0.f;
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int col = threadIdx.x * 4 + it * 1024;
-    f32x4 v = zero;
-    if (col < n) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        if (s < sk) { v.x += t[it][s].x; v.y += t[it][s].y; v.z += t[it][s].z; v.w += t[it][s].w; }
-      if (bias) { v.x += b4[it].x; v.y += b4[it].y; v.z += b4[it].z; v.w += b4[it].w; }
-      if (epilogue == CHATTS_EPI_RESID) { v.x = rs[it].x + v.x; v.y = rs[it].y + v.y; v.z = rs[it].z + v.z; v.w = rs[it].w + v.w; }
-      *reinterpret_cast<f32x4*>(c + (size_t)row * ldc + col) = v;
-      ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-    keep[it] = v;
-  }
-  if (!norm_w) return;
-  ss = block_sum<4>(ss, red);
-  const float rstd = rsqrtf(ss / (float)n + eps);
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int col = threadIdx.x * 4 + it * 1024;
-    const f32x4 v = keep[it], g = gw[it];
-    const float ov[4] = {g.x * (v.x * rstd), g.y * (v.y * rstd), g.z * (v.z * rstd), g.w * (v.w * rstd)};
-    f16q_put4(o, row, col, ov, col < n);
-  }
+  splitk_epilogue_reg_row<kIt, true>(e, row, red, [&](int col, const float (&ov)[4], bool live) { f16q_put4(o, row, col, ov, live); });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------
@@ -740,19 +693,11 @@ static bool f16q_splitk_epilogue_fits(const ChattsLinearF16qArgs* a) {
 
 static int f16q_splitk_epilogue(const ChattsLinearF16qArgs* a, int sk, hipStream_t s) {
   F16qPlanes o{reinterpret_cast<_Float16*>(a->post_hi), a->post_lo8, a->post_scale, a->ld_post, a->ld_pscale, a->planes_tiled};
-  const float* ws = reinterpret_cast<const float*>(a->workspace);
-#define CHATTS_EPI_Q(K) hipLaunchKernelGGL((splitk_epilogue_f16q_kernel<K>), dim3(a->m), dim3(256), 0, s, ws, sk, a->m, a->n, a->bias, a->resid, a->c, \
-                                           a->ldc, a->epilogue, a->post_norm_w, a->post_norm_eps, o)
-  switch ((a->n + 1023) / 1024) {
-    case 1: CHATTS_EPI_Q(1); break;
-    case 2: CHATTS_EPI_Q(2); break;
-    case 3: CHATTS_EPI_Q(3); break;
-    case 4: CHATTS_EPI_Q(4); break;
-    case 5: CHATTS_EPI_Q(5); break;
-    case 6: CHATTS_EPI_Q(6); break;
-    default: CHATTS_EPI_Q(8); break;
-  }
-#undef CHATTS_EPI_Q
+  const SplitkEpi e{reinterpret_cast<const float*>(a->workspace), sk, a->m, a->n, a->bias, a->resid, a->c, a->ldc, a->epilogue,
+                    nullptr, a->post_norm_w, a->post_norm_eps, nullptr, nullptr, 0};
+  splitk_epilogue_its((a->n + 1023) / 1024, [&](auto k) {
+    hipLaunchKernelGGL((splitk_epilogue_f16q_kernel<decltype(k)::value>), dim3(a->m), dim3(256), 0, s, e, o);
+  });
   CHATTS_CHECK_LAUNCH("splitk_epilogue_f16q");
   return CHATTS_OK;
 }

@@ -1,5 +1,5 @@
 // gemv_common.h - the arithmetic of the batch-1 weight-streaming GEMV (gemv.hip) that fixes the bits of a result: the FMA order of a
-// bf16 load, the contraction pattern of the RMSNorm sum of squares, SiLU, and the row map of a task.
+// bf16 load, SiLU, and the row map of a task (the RMSNorm sum of squares, sumsq4, is common.h's: every kernel shares it).
 #pragma once
 #include "common.h"
 
@@ -15,12 +15,6 @@ __device__ __forceinline__ float dot8(const u32x4 wv, const f32x4 xa, const f32x
   acc = fmaf(bf16_lo(wv.w), xb.z, acc);
   acc = fmaf(bf16_hi(wv.w), xb.w, acc);
   return acc;
-}
-
-// one RMSNorm partial-sum step (Qwen2RMSNorm: sum of squares in float32); ONE definition = one contraction pattern everywhere
-__device__ __forceinline__ float sumsq4(float ss, const f32x4 v) {
-  ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  return ss;
 }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }

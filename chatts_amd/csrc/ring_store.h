@@ -41,23 +41,10 @@ __device__ __forceinline__ RingUnit ring_unit(const GemmParams& p, const RingGeo
 // token = m0 + rowbase + i * 16 + (lane & 15).  MODE / PLANES are compile-time: no branches, all loads of a row block in flight at once.
 template <int MODE, bool PLANES>
 __device__ __forceinline__ void ring_store(const GemmParams& p, const f32x4 (&acc)[5][4], int fml, int tok0, int fb0, int lane, int split) {
-  typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
   const int tl = lane & 15, fq = (lane >> 4) * 4;
   auto put = [&](size_t row_off_c, size_t row_off_p, int col, const float (&v)[4]) __attribute__((always_inline)) {
-    if constexpr (PLANES) {
-#pragma clang fp contract(off)      // lo is the split of the ROUNDED float32 value (store_planes' arithmetic)
-      bf16x4_t hv, lv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const __bf16 h = (__bf16)v[r];
-        hv[r] = h;
-        lv[r] = (__bf16)(v[r] - (float)h);
-      }
-      *reinterpret_cast<bf16x4_t*>(p.c_hi + row_off_p + col) = hv;
-      *reinterpret_cast<bf16x4_t*>(p.c_lo + row_off_p + col) = lv;
-    } else {
-      *reinterpret_cast<f32x4*>(p.c + row_off_c + col) = (f32x4){v[0], v[1], v[2], v[3]};
-    }
+    if constexpr (PLANES) store_planes4(p.c_hi, p.c_lo, row_off_p, col, v);
+    else *reinterpret_cast<f32x4*>(p.c + row_off_c + col) = (f32x4){v[0], v[1], v[2], v[3]};
   };
   if constexpr (MODE == kStRaw) {
     float* ws = p.c + (size_t)split * p.m * p.n;

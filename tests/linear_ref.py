@@ -558,8 +558,11 @@ def _ring_cases():
 
 def _epi_cases():
     """the split-K epilogues, each behind the smallest producer that reaches it: splitk_epilogue_kernel (SwiGLU, or ldc % 4 != 0),
-    splitk_epilogue_v4_kernel, and with post_norm_w splitk_epilogue_norm_kernel (EPI_NORM_REG=0), splitk_epilogue_norm_reg_kernel<1> (N = 160)
-    and <2> (N = 1040), splitk_epilogue_norm_q_kernel<8, 1> and <8, 3> (M <= 16)"""
+    splitk_epilogue_v4_kernel, and with post_norm_w splitk_epilogue_norm_kernel (EPI_NORM_REG=0; sk = 3, and sk = 5: its loop over more
+    than four slabs), splitk_epilogue_norm_reg_kernel<1> (N = 160), <2> (N = 1040) and <8> (N = 6160: 7 column groups, the `default` of the
+    instantiation table), splitk_epilogue_norm_q_kernel<8, 1> and <8, 3> (M <= 16; sk = 2, sk = 5: more than four slabs, and N = 3088: a
+    row that ends inside the second batch of three column groups).  6160 and 3088 are the smallest widths past 6 x 1024 and 3 x 1024 that
+    chatts_linear accepts (N % 16 == 0): four threads hold the last column group."""
     out, i = [], 0
 
     def add(kernel, m, n, k, epi, sk, operand, opts=(), post=False, ldc_pad=0, profiles=None):
@@ -585,6 +588,12 @@ def _epi_cases():
     add("splitk_epilogue_norm_reg<1>", 17, 160, 1056, EPI_RESID, 3, "a", bm, post=True, profiles=("zero_rows",))
     add("splitk_epilogue_norm_q<8,3>", 7, 160, 320, EPI_RESID, 2, "planes_only", (("EPI_NORM_Q_GROUPS", 3),), post=True, profiles=("zero_rows",))
     add("splitk_epilogue_v4", 17, 160, 1056, EPI_NONE, 5, "a", bm, profiles=("cancel",))
+    for epi in (EPI_NONE, EPI_RESID):          # (behind the cases above: their seeds stay)
+        add("splitk_epilogue_norm", 17, 160, 1056, epi, 5, "a", bm + (("EPI_NORM_REG", 0),), post=True)
+        add("splitk_epilogue_norm_reg<8>", 17, 6160, 1056, epi, 3, "a", bm, post=True)
+        add("splitk_epilogue_norm_q<8,3>", 7, 160, 320, epi, 5, "planes_only", (("EPI_NORM_Q_GROUPS", 3),), post=True)
+        add("splitk_epilogue_norm_q<8,1>", 7, 160, 320, epi, 5, "planes_only", (("EPI_NORM_Q_GROUPS", 1),), post=True)
+        add("splitk_epilogue_norm_q<8,3>", 16, 3088, 320, epi, 2, "planes_only", (("EPI_NORM_Q_GROUPS", 3),), post=True)
     return out
 
 

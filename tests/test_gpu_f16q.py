@@ -318,6 +318,17 @@ def test_linear_f16q_forced_geometries(lib, monkeypatch, t, sk):
             _f16q_check(lib, O, epi, post, what=f"T={t} sk={sk} epi={epi} post={post}")
 
 
+def test_linear_f16q_forced_split_of_a_wide_row(lib, monkeypatch):
+    """N = 6272 = 49 x 128 under GEMM_SK = 2: 7 column groups of 1024 per row, splitk_epilogue_f16q_kernel<8> (the widest instantiation; the
+    shape above takes <1>), M = 17 (a ragged second fragment) - the float64 bars of the forced geometries, with and without post-norm"""
+    from tests.test_gpu_strides import _f16q_operands
+    monkeypatch.setenv("CHATTS_GEMM_SK", "2")
+    O = _f16q_operands(lib, 17, 6272, 1024, seed=31, tiled=False)
+    for epi in (_lib.EPI_NONE, _lib.EPI_RESID):
+        for post in (False, True):
+            _f16q_check(lib, O, epi, post, what=f"n=6272 sk=2 epi={epi} post={post}")
+
+
 @pytest.mark.parametrize("sk", [None, 2])
 def test_linear_f16q_gelu_epilogue(lib, monkeypatch, sk):
     """EPI_GELU at a shape where the picker splits K (few tiles, long K), at the picker's choice and with GEMM_SK forced to 2: the

@@ -33,9 +33,10 @@ test_gpu_attention_edges.py does), so that tools/linear_edges.py can run the sam
                                           no A to fall back on); GEMM_SK 3 honoured at K = 320 / 1088 (nk / 3 >= 1), GEMM_T in range   lr.RING
     splitk_epilogue_kernel                SwiGLU behind a split, or ldc % 4 != 0                                                    lr.EPILOGUES
     splitk_epilogue_v4_kernel             every other split of the lists above, and                                                 lr.EPILOGUES
-    splitk_epilogue_norm_kernel           post_norm_w, M > 16, EPI_NORM_REG=0                                                      lr.EPILOGUES
-    splitk_epilogue_norm_reg_kernel<1 | 2>  post_norm_w, M > 16, sk = 3, N = 160 / 1040 (its = ceil(N / 1024))                      lr.EPILOGUES
-    splitk_epilogue_norm_q_kernel<8, 1 | 3> post_norm_w, M <= 16, EPI_NORM_Q_GROUPS 1 / 3                                          lr.EPILOGUES
+    splitk_epilogue_norm_kernel           post_norm_w, M > 16, EPI_NORM_REG=0; sk = 3, and sk = 5 (the loop over more than 4 slabs)  lr.EPILOGUES
+    splitk_epilogue_norm_reg_kernel<1 | 2 | 8>  post_norm_w, M > 16, sk = 3, N = 160 / 1040 / 6160 (its = ceil(N / 1024); 7 takes <8>)  lr.EPILOGUES
+    splitk_epilogue_norm_q_kernel<8, 1 | 3> post_norm_w, M <= 16, EPI_NORM_Q_GROUPS 1 / 3; sk = 2 and 5 (more than 4 slabs), N = 160 /
+                                          1040 / 3088 (a row that ends inside the second batch of three column groups)               lr.EPILOGUES
   rmsnorm_kernel<false | true>            chatts_rmsnorm / chatts_rmsnorm_planes, hidden 4 and 5120                                  lr.RMSNORM
 K = 1056 under GEMM_SK=3 gives gemm_bf16x2_kernel three EQUAL splits of 11 K-steps (k_per_split = 352); GEMM_SK=5 is there for the shorter
 last split (224 x 4 + 160)."""
@@ -94,8 +95,9 @@ def _split(lib, a):
     return hi, lo
 
 
-def run_linear(lib, spec, c):
-    """chatts_linear on the case under the spec's options -> (out [m, ncols], post hi + lo [m, n] float64 or None), on the host"""
+def run_linear(lib, spec, c, raw=None):
+    """chatts_linear on the case under the spec's options -> (out [m, ncols], post hi + lo [m, n] float64 or None), on the host; the
+    post-norm planes themselves go into `raw` (tools/linear_edges.py --digests)"""
     m, n, k, ncols = spec.m, spec.n, spec.k, spec.ncols
     ldc = ncols + spec.ldc_pad
     a, w, bias = c["a"].to(DEV), c["w"].to(DEV), c["bias"].to(DEV)
@@ -137,6 +139,8 @@ def run_linear(lib, spec, c):
     post = None
     if spec.post:
         phi, plo = phi.cpu(), plo.cpu()
+        if raw is not None:
+            raw.update(post_hi=phi[:, :n], post_lo=plo[:, :n])
         assert torch.isnan(phi[:, n:].float()).all() and torch.isnan(plo[:, n:].float()).all(), spec
         post = phi[:, :n].float().double() + plo[:, :n].float().double()
         assert torch.isfinite(post).all(), spec
@@ -239,7 +243,7 @@ def test_gemm_ring(lib, m):
 
 def test_splitk_epilogues(lib):
     """the plain, v4 and the three post-norm split-K epilogues; under post_norm_w both c and post_hi + post_lo against their bars"""
-    assert len({s.kernel for s in lr.EPILOGUES}) == 8 and any(s.post and s.profile == "wide_norm" for s in lr.EPILOGUES)
+    assert len({s.kernel for s in lr.EPILOGUES}) == 9 and any(s.post and s.profile == "wide_norm" for s in lr.EPILOGUES)
     assert_within_bars(measure(lib, s) for s in lr.EPILOGUES)
 
 

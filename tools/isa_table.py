@@ -145,6 +145,11 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         (ro, ao), (rn, an) = compile_one(args.old, os.path.join(tmp, "old")), compile_one(new_src, os.path.join(tmp, "new"))
     names = demangle(sorted(set(ro) | set(rn)))
+    # joined by demangled name: a kernel whose parameter list changed has another mangled name in the new file
+    for d in (ro, ao, rn, an):
+        for mangled in list(d):
+            d[names.get(mangled, mangled)] = d.pop(mangled)
+    names = {n: n for n in names.values()}
     print("compiled for gfx950 with " + " ".join(b.FLAGS) + f"; hot blocks: /{args.hot}/; nothing in this table was run")
     print(f"{'kernel':58s} {'VGPRs':>10s} {'SGPRs':>10s} {'scratch':>8s} {'occ':>8s}  stream")
     counts, worse = {}, []
