@@ -103,6 +103,16 @@ class LogitControlArgs(C.Structure):
                 ("temperature_rows", c_void_p)]
 
 
+LOGIT_BIAS_MAX, LOGIT_END_IDS_MAX = 1024, 64      # CHATTS_LOGIT_BIAS_MAX / CHATTS_LOGIT_END_IDS_MAX of include/chatts_amd.h
+
+
+class LogitMaskArgs(C.Structure):
+    """ChattsLogitMaskArgs: allowed_token_ids / logit_bias / min_tokens of the rows of a selection (csrc/logit_masks.hip)"""
+    _fields_ = [("out", c_void_p), ("out_stride", c_int64), ("allow_bits", c_void_p), ("allow_stride", c_int64), ("allow_on", c_void_p),
+                ("bias_ids", c_void_p), ("bias_val", c_void_p), ("bias_n", c_void_p), ("bias_stride", c_int64),
+                ("end_ids", c_void_p), ("end_n", c_void_p), ("min_tokens", c_void_p), ("end_stride", c_int64)]
+
+
 class DecoderConfig(C.Structure):
     _fields_ = [("hidden", c_int), ("n_layers", c_int), ("n_q", c_int), ("n_kv", c_int), ("head_dim", c_int),
                 ("inter", c_int), ("vocab_local", c_int64), ("vocab_offset", c_int64), ("rms_eps", c_float),
@@ -225,6 +235,12 @@ SIGNATURES = {
                                                         c_void_p, c_void_p, c_int, C.POINTER(SamplingArgs),
                                                         C.POINTER(LogitControlArgs), c_void_p]),
     "chatts_decoder_set_logit_controls": (c_int, [c_void_p, C.POINTER(LogitControlArgs)]),
+    "chatts_decoder_select_tokens_masked": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                    c_void_p, c_void_p, c_int, C.POINTER(SamplingArgs), C.POINTER(LogitControlArgs),
+                                                    C.POINTER(LogitMaskArgs), c_void_p]),
+    "chatts_decoder_set_logit_masks": (c_int, [c_void_p, C.POINTER(LogitMaskArgs)]),
+    # logit masks (logit_masks.hip)
+    "chatts_logit_masks_apply": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, C.POINTER(LogitMaskArgs), c_void_p, c_void_p]),
     # logit controls (logit_controls.hip)
     "chatts_logit_controls_workspace": (c_size_t, [c_int]),
     "chatts_logit_controls_apply": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, C.POINTER(LogitControlArgs), c_void_p, c_size_t,

@@ -194,6 +194,24 @@ __device__ __forceinline__ void rope_kv_head(float a, float b, int h, int pos, i
 
 inline hipStream_t as_stream(chatts_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// What chatts_logit_masks_apply refuses about its per-row arrays, for ids vocab_offset .. vocab_offset + vocab - 1; also called by the
+// decoder's selection AHEAD of its tensor-parallel gather (a refusal on one rank must not leave the others waiting in the collective).
+inline int logit_mask_arrays_check(const ChattsLogitMaskArgs* a, int64_t vocab, int64_t vocab_offset, const int32_t* step_dev,
+                                   const char* who) {
+  const bool allow = a->allow_bits && a->allow_on;
+  const bool bias = a->bias_ids && a->bias_val && a->bias_n;
+  const bool ends = a->end_ids && a->end_n && a->min_tokens;
+  const int64_t words = (vocab_offset + vocab + 31) / 32;
+  CHATTS_REQUIRE(!allow || a->allow_stride >= words, CHATTS_E_BADARG, "%s: allow_stride %lld is below the %lld words of ids 0 .. %lld",
+                 who, (long long)a->allow_stride, (long long)words, (long long)(vocab_offset + vocab - 1));
+  CHATTS_REQUIRE(!bias || (a->bias_stride >= 1 && a->bias_stride <= CHATTS_LOGIT_BIAS_MAX), CHATTS_E_BADARG,
+                 "%s: bias_stride %lld must be in 1 .. %d", who, (long long)a->bias_stride, CHATTS_LOGIT_BIAS_MAX);
+  CHATTS_REQUIRE(!ends || (a->end_stride >= 1 && a->end_stride <= CHATTS_LOGIT_END_IDS_MAX), CHATTS_E_BADARG,
+                 "%s: end_stride %lld must be in 1 .. %d", who, (long long)a->end_stride, CHATTS_LOGIT_END_IDS_MAX);
+  CHATTS_REQUIRE(!ends || step_dev, CHATTS_E_BADARG, "%s: min_tokens needs the rows' step counters (step_dev)", who);
+  return CHATTS_OK;
+}
+
 // ---- stage ranges for traces (api.hip): roctx push / pop around the host-side enqueue of a stage, resolved with dlopen at first use
 // (librocprofiler-sdk-roctx.so; absent library = no-ops), so that `rocprofv3 --marker-trace --kernel-trace` reads by stage - ts_encode,
 // prefill, layer.attn / layer.mlp, decode_step, logits, select_tokens - instead of by kernel name.  Ranges mark where work is ENQUEUED;

@@ -50,6 +50,8 @@ struct ChattsDecoder {
   ChattsSamplingArgs sa{};
   bool controls = false;    // logit controls (penalties / min_p) ahead of every selection, with `lc` (chatts_decoder_set_logit_controls)
   ChattsLogitControlArgs lc{};
+  bool masks = false;       // logit masks (allowed_token_ids / logit_bias / min_tokens) ahead of the controls, with `lm` (chatts_decoder_set_logit_masks)
+  ChattsLogitMaskArgs lm{};
   ChattsTpComm* tp = nullptr;   // tensor-parallel exchange (borrowed); required by the whole-step entry points when tp_world > 1
   bool prefill_f16q = false; // opt-in parity-grade mode (chatts_decoder_set_prefill_f16q): prefill chunks of >= 96 rows on the f16 + e4m3 operand split
   bool prefill_fp8 = false; // SPEED MODE (chatts_decoder_set_prefill_fp8): prefill chunks of >= 16 rows multiply fp8 x fp8 (gemm_fp8.hip)
@@ -380,6 +382,14 @@ extern "C" int chatts_decoder_set_logit_controls(ChattsDecoder* d, const ChattsL
   return CHATTS_OK;
 }
 
+extern "C" int chatts_decoder_set_logit_masks(ChattsDecoder* d, const ChattsLogitMaskArgs* lm) {
+  CHATTS_REQUIRE(d, CHATTS_E_BADARG, "decoder_set_logit_masks: null decoder");
+  if (lm) CHATTS_REQUIRE(lm->out, CHATTS_E_BADARG, "decoder_set_logit_masks: args.out is required");
+  d->masks = lm != nullptr;
+  if (lm) d->lm = *lm;
+  return CHATTS_OK;
+}
+
 // ---- token selection and logprobs ------------------------------------------------------------------------------------------------
 // What a rank must have before it may gather the full-vocabulary logits into buffers.logits_full.  Call it, and every other check of
 // the caller, AHEAD of chatts_allgather: a refusal on one rank must not leave the others waiting in the collective.
@@ -391,37 +401,55 @@ static int require_full_logits_tp(const ChattsDecoder* d, int batch, int64_t log
   return CHATTS_OK;
 }
 
-// Selection with the logit controls on: penalised logits into lc->out, the TP = 1 selection on them, the chosen tokens into the state.
+// Selection with the logit masks and / or the logit controls on: masked logits into lm->out, penalised logits (of those) into lc->out,
+// the TP = 1 selection on the last buffer written, the chosen tokens into the controls' state.
 // Tensor parallel: every rank gathers the full-vocabulary logits and does the same work on the same bytes -> the same token.
-static int select_controlled(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride, int64_t* token, float* token_logit,
-                             int64_t* out_tokens, int64_t out_stride, int32_t* step_dev, int32_t* pos_dev, int pos_limit,
-                             const ChattsSamplingArgs* sa, const ChattsLogitControlArgs* lc, chatts_stream_t stream) {
+static int select_processed(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride, int64_t* token, float* token_logit,
+                            int64_t* out_tokens, int64_t out_stride, int32_t* step_dev, int32_t* pos_dev, int pos_limit,
+                            const ChattsSamplingArgs* sa, const ChattsLogitControlArgs* lc, const ChattsLogitMaskArgs* lm,
+                            chatts_stream_t stream) {
   const ChattsDecoderConfig& c = d->cfg;
   int64_t vocab = c.vocab_local, offset = c.vocab_offset;
   int rc;
   if (c.tp_world > 1) {
-    if ((rc = require_full_logits_tp(d, batch, logits_stride, "decoder_select_tokens", "logit controls under tensor parallelism need")) != 0)
+    if ((rc = require_full_logits_tp(d, batch, logits_stride, "decoder_select_tokens",
+                                     "logit controls and logit masks under tensor parallelism need")) != 0)
       return rc;
     vocab = c.vocab_local * c.tp_world; offset = 0;
   }
-  CHATTS_REQUIRE(lc->state && lc->out && lc->state_stride >= vocab && lc->out_stride >= vocab, CHATTS_E_BADARG,
-                 "decoder_select_tokens: logit controls need state and out rows of >= %lld cells", (long long)vocab);
-  CHATTS_REQUIRE(d->b.workspace && d->b.workspace_bytes >= chatts_logit_controls_workspace(batch), CHATTS_E_WORKSPACE,
-                 "decoder_select_tokens: the workspace is too small for the logit controls of %d rows", batch);
+  if (lc) {
+    CHATTS_REQUIRE(lc->state && lc->out && lc->state_stride >= vocab && lc->out_stride >= vocab, CHATTS_E_BADARG,
+                   "decoder_select_tokens: logit controls need state and out rows of >= %lld cells", (long long)vocab);
+    CHATTS_REQUIRE(d->b.workspace && d->b.workspace_bytes >= chatts_logit_controls_workspace(batch), CHATTS_E_WORKSPACE,
+                   "decoder_select_tokens: the workspace is too small for the logit controls of %d rows", batch);
+  }
+  if (lm) {
+    CHATTS_REQUIRE(lm->out && lm->out_stride >= vocab && lm->out != logits && lm->out != d->b.logits_full && (!lc || lm->out != lc->out),
+                   CHATTS_E_BADARG, "decoder_select_tokens: logit masks need out rows of >= %lld cells in a buffer of their own",
+                   (long long)vocab);
+    if ((rc = logit_mask_arrays_check(lm, vocab, offset, step_dev, "decoder_select_tokens")) != 0) return rc;
+  }
   if (c.tp_world > 1) {
     if ((rc = chatts_allgather(d->tp, logits, d->b.logits_full, batch, c.vocab_local, stream)) != 0) return rc;
     logits = d->b.logits_full; logits_stride = vocab;
   }
-  // (the split-K / attention workspace is idle here: every kernel that used it is ahead of this call on the stream)
-  if ((rc = chatts_logit_controls_apply(logits, batch, logits_stride, vocab, offset, lc, d->b.workspace, d->b.workspace_bytes, stream)) != 0)
-    return rc;
+  if (lm) {
+    if ((rc = chatts_logit_masks_apply(logits, batch, logits_stride, vocab, offset, lm, step_dev, stream)) != 0) return rc;
+    logits = lm->out; logits_stride = lm->out_stride;
+  }
+  if (lc) {
+    // (the split-K / attention workspace is idle here: every kernel that used it is ahead of this call on the stream)
+    if ((rc = chatts_logit_controls_apply(logits, batch, logits_stride, vocab, offset, lc, d->b.workspace, d->b.workspace_bytes, stream)) != 0)
+      return rc;
+    logits = lc->out; logits_stride = lc->out_stride;
+  }
   if (sa)
-    rc = chatts_sample_batched(lc->out, batch, lc->out_stride, vocab, offset, sa, token, token_logit, out_tokens, out_stride, step_dev,
+    rc = chatts_sample_batched(logits, batch, logits_stride, vocab, offset, sa, token, token_logit, out_tokens, out_stride, step_dev,
                                pos_dev, pos_limit, stream);
   else
-    rc = chatts::argmax_batched_scratch(lc->out, batch, lc->out_stride, vocab, offset, token, token_logit, out_tokens, out_stride, step_dev,
+    rc = chatts::argmax_batched_scratch(logits, batch, logits_stride, vocab, offset, token, token_logit, out_tokens, out_stride, step_dev,
                                         pos_dev, pos_limit, d->b.workspace, d->b.workspace_bytes, reinterpret_cast<hipStream_t>(stream));
-  if (rc) return rc;
+  if (rc || !lc) return rc;
   return chatts_logit_state_update(lc->state, lc->state_stride, batch, vocab, offset, token, stream);
 }
 
@@ -433,20 +461,30 @@ extern "C" int chatts_decoder_select_tokens(ChattsDecoder* d, const float* logit
                                                  pos_dev, pos_limit, override_sa, nullptr, stream);
 }
 
-// Greedy / sampled token for `batch` logits rows of this rank, agreed across the TP ranks (see the header).
 extern "C" int chatts_decoder_select_tokens_controlled(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride,
                                                        int64_t* token, float* token_logit, int64_t* out_tokens, int64_t out_stride,
                                                        int32_t* step_dev, int32_t* pos_dev, int pos_limit,
                                                        const ChattsSamplingArgs* override_sa, const ChattsLogitControlArgs* override_lc,
                                                        chatts_stream_t stream) {
+  return chatts_decoder_select_tokens_masked(d, logits, batch, logits_stride, token, token_logit, out_tokens, out_stride, step_dev, pos_dev,
+                                             pos_limit, override_sa, override_lc, nullptr, stream);
+}
+
+// Greedy / sampled token for `batch` logits rows of this rank, agreed across the TP ranks (see the header).
+extern "C" int chatts_decoder_select_tokens_masked(ChattsDecoder* d, const float* logits, int batch, int64_t logits_stride,
+                                                   int64_t* token, float* token_logit, int64_t* out_tokens, int64_t out_stride,
+                                                   int32_t* step_dev, int32_t* pos_dev, int pos_limit,
+                                                   const ChattsSamplingArgs* override_sa, const ChattsLogitControlArgs* override_lc,
+                                                   const ChattsLogitMaskArgs* override_lm, chatts_stream_t stream) {
   CHATTS_REQUIRE(d && logits && token && batch >= 1, CHATTS_E_BADARG, "decoder_select_tokens: bad arguments");
   StageRange stage("chatts.select_tokens");
   const ChattsDecoderConfig& c = d->cfg;
   const ChattsSamplingArgs* sa = override_sa ? override_sa : (d->sampling ? &d->sa : nullptr);
   const ChattsLogitControlArgs* lc = override_lc ? override_lc : (d->controls ? &d->lc : nullptr);
-  if (lc)
-    return select_controlled(d, logits, batch, logits_stride, token, token_logit, out_tokens, out_stride, step_dev, pos_dev, pos_limit, sa,
-                             lc, stream);
+  const ChattsLogitMaskArgs* lm = override_lm ? override_lm : (d->masks ? &d->lm : nullptr);
+  if (lc || lm)
+    return select_processed(d, logits, batch, logits_stride, token, token_logit, out_tokens, out_stride, step_dev, pos_dev, pos_limit, sa,
+                            lc, lm, stream);
   if (c.tp_world <= 1) {
     if (sa)
       return chatts_sample_batched(logits, batch, logits_stride, c.vocab_local, c.vocab_offset, sa, token, token_logit, out_tokens,
@@ -1073,8 +1111,8 @@ extern "C" int chatts_decoder_spec_step(ChattsDecoder* d, const ChattsSpecArgs* 
   CHATTS_REQUIRE(a->ngram_min >= 1 && a->ngram_max >= a->ngram_min && a->ngram_max <= CHATTS_SPEC_MAX_NGRAM, CHATTS_E_BADARG,
                  "decoder_spec_step: n-gram sizes %d..%d must satisfy 1 <= min <= max <= %d", a->ngram_min, a->ngram_max, CHATTS_SPEC_MAX_NGRAM);
   CHATTS_REQUIRE(d->cfg.tp_world <= 1, CHATTS_E_BADARG, "decoder_spec_step: tensor_parallel_size 1 only (tp_world = %d)", d->cfg.tp_world);
-  CHATTS_REQUIRE(!d->sampling && !d->controls, CHATTS_E_BADARG,
-                 "decoder_spec_step: greedy decoding only (a sampler or logit controls are set on the decoder)");
+  CHATTS_REQUIRE(!d->sampling && !d->controls && !d->masks, CHATTS_E_BADARG,
+                 "decoder_spec_step: greedy decoding only (a sampler, logit controls or logit masks are set on the decoder)");
   const ChattsDecoderConfig& c = d->cfg;
   const int R = a->k + 1;
   CHATTS_REQUIRE(R <= d->b.t_max && R < c.max_ctx, CHATTS_E_SHAPE, "decoder_spec_step: %d rows exceed the buffers (%d) or the context", R,

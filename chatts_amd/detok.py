@@ -79,9 +79,11 @@ class StopChecker:
     """The stop rule over a growing token sequence.  push(new_ids) -> None, or (j, text, matched string): the sequence stops after
     its first j tokens with that final text.  `released` is the text a stream may show so far: text(j) without its held-back tail."""
 
-    def __init__(self, tokenizer, stop, include_stop_str_in_output=False):
+    def __init__(self, tokenizer, stop, include_stop_str_in_output=False, min_tokens=0):
         self.tok, self.stops, self.include = tokenizer, normalize_stop(stop), bool(include_stop_str_in_output)
         self.ids, self.released, self.hit = [], "", None
+        # min_tokens (vLLM's rule): no stop string is searched in the text the first min_tokens tokens produced - `base` characters
+        self.min_tokens, self.base = max(0, int(min_tokens or 0)), 0
 
     def push(self, new_ids):
         if self.hit is not None:
@@ -89,8 +91,13 @@ class StopChecker:
         for t in new_ids:
             self.ids.append(int(t))
             text = stable_text(self.tok, self.ids)
-            m = find_stop(text, self.stops)
+            if len(self.ids) <= self.min_tokens:
+                self.base = len(text)
+                self.released = text if text.startswith(self.released) else self.released
+                continue
+            m = find_stop(text[self.base:], self.stops) if self.base <= len(text) else None
             if m is not None:
+                m = (m[0] + self.base,) + tuple(m[1:])
                 end = m[0] + (len(m[1]) if self.include else 0)
                 self.released = text[:end]
                 self.hit = (len(self.ids), self.released, m[1])

@@ -18,7 +18,7 @@ from collections import deque
 
 import numpy as np
 
-from .sampling import (NO_CONTROLS, REQUEST_FIELDS, request_settings, validate_controls, validate_n,  # noqa: F401  (re-exported)
+from .sampling import (END_IDS_MAX, NO_CONTROLS, NO_MASKS, REQUEST_FIELDS, request_settings, validate_controls, validate_n,  # noqa: F401  (re-exported)
                        validate_sampling)
 
 
@@ -45,6 +45,7 @@ class Request:
         self.sampling = (0.0, 0, 1.0, 0) if key is None else key       # (temperature, top_k, top_p, seed): the slot's settings
         self.sampling_key = key if not mixed else "rows" if key else None
         self.controls = s["controls"]        # (repetition_penalty, frequency_penalty, presence_penalty, min_p)
+        self.masks = tuple(s["masks"])       # (logit_bias {id: bias} or None, allowed_token_ids or None, min_tokens)
         self.tokens, self.sent, self.finished, self.finish_reason = [], 0, False, None
         self.prompt_tokens = 0
         # logprobs=k: one (logprob, rank, [(id, logprob)] * k) entry per token of `tokens`, grown with it; None when not asked
@@ -108,9 +109,10 @@ class Engine:
     def check(self, **settings):
         """The one check of a request's settings (sampling.REQUEST_FIELDS): their value ranges, and what THIS engine cannot serve - n >
         max_num_seqs, n > 1 on a model without per-slot sampling settings or without a fork, stop strings without a tokenizer, logit
-        controls or logprobs on a model without them.  ValueError, or -> the normalised settings (sampling.request_settings).
+        controls, logit masks or logprobs on a model without them, ids of logit_bias / allowed_token_ids outside the model's vocabulary,
+        more than 64 ids for min_tokens to keep away.  ValueError, or -> the normalised settings (sampling.request_settings).
         add_request calls it; EngineThread calls it BEFORE a request is announced to the follower ranks."""
-        s = request_settings(**settings, max_logprobs=self.max_logprobs, max_num_seqs=self.nslots)
+        s = request_settings(**settings, max_logprobs=self.max_logprobs, max_num_seqs=self.nslots, vocab_size=self.vocab_size)
         if s["n"] > 1 and not self.mixed:
             raise ValueError("n > 1 needs a model with per-slot sampling settings (set_slot_sampling)")
         if s["n"] > 1 and not hasattr(self.model, "admit_fork"):
@@ -119,6 +121,15 @@ class Engine:
             raise ValueError("stop strings need a tokenizer (the engine's processor has none)")
         if s["controls"] != NO_CONTROLS and not hasattr(self.model, "set_slot_controls"):
             raise ValueError("this model does not apply repetition / frequency / presence penalties or min_p")
+        if tuple(s["masks"]) != NO_MASKS:
+            if not hasattr(self.model, "set_slot_masks"):
+                raise ValueError("this model does not apply logit_bias, allowed_token_ids or min_tokens")
+            ends = {t for t in set(() if s["ignore_eos"] else self._model_eos()) | set(s["stop_token_ids"]) if t is not None}
+            V = self.vocab_size                      # (request_settings refused stop_token_ids outside it when min_tokens > 0)
+            ends = {t for t in ends if V is None or 0 <= t < V}       # (an EOS id the logits do not cover can never be chosen)
+            if s["masks"][2] and len(ends) > END_IDS_MAX:
+                raise ValueError(f"min_tokens: {len(ends)} ids would end the sequence (stop_token_ids and the EOS ids), at most "
+                                 f"{END_IDS_MAX} are accepted")
         if s["logprobs"] is not None and not hasattr(self.model, "set_logprobs"):
             raise ValueError("this model does not compute logprobs")
         return s
@@ -135,11 +146,20 @@ class Engine:
         s = self.check(**settings)
         if s["seed"] is None:
             s["seed"] = ((self._rid + 1) * 2654435761) & 0xFFFFFFFF if self.mixed else 0
-        e = self.model.config.eos_token_id
         self._rid += 1
-        r = Request(self._rid, prompt, list(timeseries or []), on_tokens, list(e) if isinstance(e, (list, tuple)) else [e], self.mixed, **s)
+        r = Request(self._rid, prompt, list(timeseries or []), on_tokens, self._model_eos(), self.mixed, **s)
         self.waiting.append(r)
         return r
+
+    def _model_eos(self):
+        e = self.model.config.eos_token_id
+        return list(e) if isinstance(e, (list, tuple)) else [e]
+
+    @property
+    def vocab_size(self):
+        """the ids the model's logits cover (None for a stand-in model without a shard plan: the ids are then checked as int32 only)"""
+        plan = getattr(self.model, "plan", None)
+        return None if plan is None else int(plan.vocab) * int(plan.world)
 
     @property
     def max_logprobs(self):
@@ -267,10 +287,12 @@ class Engine:
         return "wait" if self._running() else "never"
 
     def _write_settings(self, slot, r):
-        """the slot's sampling settings and logit controls, before its first token is drawn (per-slot mode)"""
+        """the slot's sampling settings, logit controls and logit masks, before its first token is drawn (per-slot mode)"""
         self.model.set_slot_sampling(slot, *r.sampling)
         if hasattr(self.model, "set_slot_controls"):
             self.model.set_slot_controls(slot, *r.controls)
+        if hasattr(self.model, "set_slot_masks"):        # (a tenant with none of the three resets the slot's rows)
+            self.model.set_slot_masks(slot, *r.masks, end_ids=sorted(i for i in r.eos if i is not None))
 
     def _place(self, r, s, st=None):
         """the admission of r into slot s is complete: it runs from now on (n > 1: its children, in s and the forked slots)"""
@@ -335,17 +357,28 @@ class Engine:
                                                f"request needs {sum(self._needs(r))} KV positions, more than the block pool can hold "
                                                f"({m.kv_stats()})"), done)
                     continue
-            items, kids = [], []
+            items, kids, admitted = [], [], []
             for r in group:
                 ids, ser, lens = r._enc
                 s = m.pick_slot(free, m._request_idents(ids, ser, lens))      # the slot whose resident prefix matches best
                 free.remove(s)
                 kids = free[:r.n - 1]
-                items.append((s, ids, ser, lens, r.max_tokens))
                 self.waiting.remove(r)
                 if self.mixed:                           # every sequence's own settings
-                    for c, sl in zip(r.outputs, [s] + kids):
-                        self._write_settings(sl, c)
+                    try:
+                        for c, sl in zip(r.outputs, [s] + kids):
+                            self._write_settings(sl, c)
+                    except Exception as e:               # settings the model refuses fail THAT request: its slot is free again
+                        free.append(s)
+                        free.sort()
+                        kids = []
+                        self._fail(r, e, done)
+                        continue
+                items.append((s, ids, ser, lens, r.max_tokens))
+                admitted.append(r)
+            group = admitted
+            if not group:
+                continue
             try:
                 if not self._start(group, items, kids):
                     return
@@ -373,6 +406,8 @@ class Engine:
             self._mode("logprobs", lambda r: r.logprob_k is not None, bool(getattr(m, "_logprobs_on", False)), m.set_logprobs)
         if hasattr(m, "set_logit_controls"):
             self._mode("controls", lambda r: r.controls != NO_CONTROLS, bool(getattr(m, "_controls_on", False)), m.set_logit_controls)
+        if hasattr(m, "set_logit_masks"):
+            self._mode("masks", lambda r: r.masks != NO_MASKS, bool(getattr(m, "_masks_on", False)), m.set_logit_masks)
         while not self.mixed and not running and self.waiting and self.waiting[0].sampling_key != self.active_key:
             try:
                 self._apply_sampling(self.waiting[0].sampling_key)
@@ -477,7 +512,7 @@ class Engine:
         here (a stop string matched: the tokens generated past the match are dropped); otherwise r.text is what a stream may show."""
         from .detok import StopChecker
         if r.checker is None:
-            r.checker = StopChecker(self.processor.tokenizer, r.stop, r.include_stop)
+            r.checker = StopChecker(self.processor.tokenizer, r.stop, r.include_stop, r.masks[2])
         limit = min(len(toks), r.max_tokens) if cut is None else cut
         seen = len(r.checker.ids)
         hit = r.checker.push(toks[seen:limit])

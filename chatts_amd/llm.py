@@ -161,8 +161,10 @@ class LLM:
         sp = sampling_params or SamplingParams()
         if sp.logprobs is not None and sp.logprobs > self.model.max_logprobs:
             raise ValueError(f"logprobs={sp.logprobs} exceeds max_logprobs={self.model.max_logprobs} (LLM(max_logprobs=...))")
-        if getattr(sp, "n", 1) > 1 or getattr(sp, "stop", None):
-            return self._generate_engine(prompts, sp)         # per-slot seeds / stop strings: through an Engine on this model
+        masked = bool(getattr(sp, "logit_bias", None) or getattr(sp, "allowed_token_ids", None) or getattr(sp, "min_tokens", 0))
+        if getattr(sp, "n", 1) > 1 or getattr(sp, "stop", None) or masked:
+            return self._generate_engine(prompts, sp)         # per-slot seeds / stop strings / logit masks: through an Engine on this model
+        self.model.set_logit_masks(False)                     # per call, like the modes below: a plain call runs the plain selection
         self.model.set_logprobs(sp.logprobs is not None)      # per call, like the sampling mode (a switch re-captures the graphs)
         controls = (sp.repetition_penalty, sp.frequency_penalty, sp.presence_penalty, sp.min_p)
         if controls == (1.0, 0.0, 0.0, 0.0):
@@ -209,6 +211,7 @@ class LLM:
         kw = {k: getattr(sp, k) for k in REQUEST_FIELDS}
         if sp.seed is None:
             kw["seed"] = self._seed
+        eng.check(**kw)                            # (the ids of logit_bias / allowed_token_ids against this model's vocabulary) before anything runs
         reqs = [eng.add_request(prompt, timeseries=series, **kw) for prompt, series in requests]
         eng.run_until_done()
         tok = self.processor.tokenizer

@@ -217,6 +217,9 @@ class ChatTSForCausalLM:
         # logit controls (set_logit_controls): repetition / frequency / presence penalties and min_p ahead of every selection, from
         # per-slot arrays and a per-slot state [max_batch, vocab] allocated on first use
         self._controls_on = False
+        # logit masks (set_logit_masks): allowed_token_ids / logit_bias / min_tokens ahead of the controls, from per-slot arrays
+        # allocated on first use
+        self._masks_on = False
         self.layers = []
         self.loaded = set()
 
@@ -1011,6 +1014,105 @@ class ChatTSForCausalLM:
         _lib.check(self.lib.chatts_logit_state_reset(B["lc_state"][slot].data_ptr(), B["lc_state"].shape[1], 0,
                                                      _lib.ptr(prompt) if prompt.numel() else None, prompt.numel(), _lib.stream_ptr()))
 
+    # ---- logit masks: allowed_token_ids / logit_bias / min_tokens (csrc/logit_masks.hip) ------------------------------------------------
+    def _mask_buffers(self):
+        B = self.buf
+        if "lm_out" not in B:
+            dev, n, V = self.device, max(1, self.max_batch), self.plan.vocab * self.plan.world
+            i32 = dict(dtype=torch.int32, device=dev)
+            B["lm_out"] = torch.zeros((n, V), dtype=torch.float32, device=dev)      # the masked logits the controls / the selection read
+            B["lm_allow"] = torch.zeros((n, (V + 31) // 32), **i32)                 # bit of id i: word i / 32, bit i % 32
+            B["lm_allow_on"] = torch.zeros(n, **i32)
+            B["lm_bias_ids"] = torch.zeros((n, _lib.LOGIT_BIAS_MAX), **i32)
+            B["lm_bias_val"] = torch.zeros((n, _lib.LOGIT_BIAS_MAX), dtype=torch.float32, device=dev)
+            B["lm_bias_n"] = torch.zeros(n, **i32)
+            B["lm_end_ids"] = torch.zeros((n, _lib.LOGIT_END_IDS_MAX), **i32)
+            B["lm_end_n"] = torch.zeros(n, **i32)
+            B["lm_min_tokens"] = torch.zeros(n, **i32)
+        return B
+
+    def _mask_args(self, slot):
+        B = self._mask_buffers()
+        return _lib.LogitMaskArgs(out=B["lm_out"][slot:].data_ptr(), out_stride=B["lm_out"].shape[1],
+                                  allow_bits=B["lm_allow"][slot:].data_ptr(), allow_stride=B["lm_allow"].shape[1],
+                                  allow_on=B["lm_allow_on"][slot:].data_ptr(), bias_ids=B["lm_bias_ids"][slot:].data_ptr(),
+                                  bias_val=B["lm_bias_val"][slot:].data_ptr(), bias_n=B["lm_bias_n"][slot:].data_ptr(),
+                                  bias_stride=_lib.LOGIT_BIAS_MAX, end_ids=B["lm_end_ids"][slot:].data_ptr(),
+                                  end_n=B["lm_end_n"][slot:].data_ptr(), min_tokens=B["lm_min_tokens"][slot:].data_ptr(),
+                                  end_stride=_lib.LOGIT_END_IDS_MAX)
+
+    def set_logit_masks(self, on):
+        """Logit masks on / off for every following selection.  On: each selection (decode steps, first tokens of every admission
+        path) first writes the masked logits of its rows (allowed_token_ids, logit_bias, min_tokens from the per-slot arrays) to a buffer
+        of their own; the penalties (when on) read that buffer, and the selection the last one written.  The raw logits - and so the
+        logprobs - are untouched.  A switch drops the captured decode graphs; off, the steps are exactly what they are without the
+        feature.  set_slot_masks switches it on when a slot needs it; the engine switches it off after greedy_return_steps iterations
+        without a request that does."""
+        on = bool(on)
+        if on == self._masks_on:
+            return
+        if on and self.plan.world > 1 and self._tp is None:
+            raise NotImplementedError("logit_bias / allowed_token_ids / min_tokens under tensor parallelism need the peer-to-peer "
+                                      "exchange (use_p2p=True)")
+        if on:
+            args = self._mask_args(0)
+            _lib.check(self.lib.chatts_decoder_set_logit_masks(self._decoder, C.byref(args)))
+        else:
+            _lib.check(self.lib.chatts_decoder_set_logit_masks(self._decoder, None))
+            for k in ("lm_allow_on", "lm_bias_n", "lm_end_n", "lm_min_tokens"):      # no slot's settings survive the mode
+                self.buf[k].zero_()
+        self._masks_on = on
+        self._drop_graphs()
+
+    def check_masks(self, logit_bias=None, allowed_token_ids=None, min_tokens=0, end_ids=(), max_tokens=None):
+        """-> (bias {id: float} or None, allowed ids or None, min_tokens, sorted end ids inside the vocabulary); ValueError outside the
+        ranges of sampling.validate_masks for THIS model's vocabulary (Engine.check / the server refuse a min_tokens request whose
+        stop_token_ids lie outside it; here such ids are dropped, as they were inert before)"""
+        from .sampling import validate_masks
+        V = self.plan.vocab * self.plan.world
+        ends = sorted({int(t) for t in (end_ids or ()) if t is not None and 0 <= int(t) < V})      # (an id outside the vocabulary can never
+        bias, allowed, m = validate_masks(logit_bias, allowed_token_ids, min_tokens, max_tokens, V, ends)    # be chosen: nothing to keep away)
+        return bias, allowed, m, ends
+
+    def set_slot_masks(self, slot, logit_bias=None, allowed_token_ids=None, min_tokens=0, end_ids=()):
+        """logit_bias / allowed_token_ids / min_tokens of the sequence in cache slot `slot`, with vLLM's names and meaning; end_ids: the
+        ids that would end it (its stop_token_ids and the EOS ids it obeys), kept away while it has fewer than min_tokens tokens.  Plain
+        device copies, no re-capture.  Values other than the defaults switch the mode on (set_logit_masks); all-default values never
+        allocate anything, and reset the slot's rows while the mode is on (nothing leaks from the slot's previous tenant)."""
+        bias, allowed, m, ends = self.check_masks(logit_bias, allowed_token_ids, min_tokens, end_ids)
+        if not ends:
+            m = 0                                    # nothing could end the sequence: min_tokens has nothing to keep away
+        if bias is not None or allowed is not None or m:
+            self.set_logit_masks(True)
+        elif not self._masks_on:                     # (switching the mode off cleared every slot's flags and counts)
+            return
+        B, dev, slot = self._mask_buffers(), self.device, int(slot)
+        if allowed is not None:
+            bits = np.zeros(B["lm_allow"].shape[1], dtype=np.uint32)
+            ids = np.asarray(allowed, dtype=np.int64)
+            np.bitwise_or.at(bits, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+            B["lm_allow"][slot].copy_(torch.from_numpy(bits.view(np.int32)).to(dev))
+        B["lm_allow_on"][slot] = int(allowed is not None)
+        if bias is not None:
+            ids = sorted(bias)
+            B["lm_bias_ids"][slot, :len(ids)].copy_(torch.tensor(ids, dtype=torch.int32).to(dev))
+            B["lm_bias_val"][slot, :len(ids)].copy_(torch.tensor([bias[i] for i in ids], dtype=torch.float32).to(dev))
+        B["lm_bias_n"][slot] = len(bias or ())
+        if m:
+            B["lm_end_ids"][slot, :len(ends)].copy_(torch.tensor(ends, dtype=torch.int32).to(dev))
+        B["lm_end_n"][slot] = len(ends) if m else 0
+        B["lm_min_tokens"][slot] = m
+
+    def _request_masks(self, masks, n, max_new_tokens):
+        """masks argument of generate_batch -> one checked dict or None per request"""
+        per = list(masks) if isinstance(masks, (list, tuple)) else [masks] * n
+        if len(per) != n:
+            raise ValueError("masks: one value per request")
+        for c in per:
+            if c is not None:
+                self.check_masks(**c, max_tokens=max_new_tokens)
+        return per
+
     def set_logprobs(self, on):
         """Token logprobs on / off for every following selection.  On: each selection (decode steps, first tokens of every admission
         path) is followed by chatts_decoder_logprobs into the per-slot rings - log_softmax of the raw logits, the chosen token's rank and
@@ -1073,6 +1175,9 @@ class ChatTSForCausalLM:
             return
         if self._controls_on:
             raise NotImplementedError("logit controls are not available on the host-driven tensor-parallel path (use_p2p=False)")
+        if self._masks_on:
+            raise NotImplementedError("logit_bias / allowed_token_ids / min_tokens are not available on the host-driven tensor-parallel "
+                                      "path (use_p2p=False)")
         lib, st, B = self.lib, _lib.stream_ptr(), self.buf
         self._select_token_host_tp()
         if self._logprobs_on:     # every rank: the same kernel on the same gathered logits
@@ -1088,7 +1193,13 @@ class ChatTSForCausalLM:
         sampling: SamplingArgs for this call, None = the decoder's own setting."""
         B = self.buf
         sa = None if sampling is None else C.byref(sampling)
-        if self._controls_on:          # this single-row call sees row 0: hand it the slot's state and settings
+        if self._masks_on:             # this single-row call sees row 0: hand it the slot's settings (and state)
+            lm, lc = self._mask_args(slot), self._control_args(slot) if self._controls_on else None
+            _lib.check(self.lib.chatts_decoder_select_tokens_masked(
+                self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
+                B["token_logit_all"][slot:].data_ptr(), B["out_tokens_all"][slot].data_ptr(), out_stride,
+                B["step_all"][slot:].data_ptr(), None, 0, sa, None if lc is None else C.byref(lc), C.byref(lm), _lib.stream_ptr()))
+        elif self._controls_on:        # this single-row call sees row 0: hand it the slot's state and settings
             lc = self._control_args(slot)
             _lib.check(self.lib.chatts_decoder_select_tokens_controlled(
                 self._decoder, _lib.ptr(B["logits"]), 1, self.plan.vocab, B["token_all"][slot:].data_ptr(),
@@ -1215,9 +1326,10 @@ class ChatTSForCausalLM:
         return B
 
     def _spec_allowed(self):
-        """may the selected sequence take the speculative step now?  Greedy, no logit controls, no logprobs, one sequence, TP = 1."""
+        """may the selected sequence take the speculative step now?  Greedy, no logit controls, no logit masks, no logprobs, one
+        sequence, TP = 1."""
         return (self.plan.world == 1 and self.max_batch == 1 and getattr(self, "_sampling_key", None) is None
-                and not self._controls_on and not self._logprobs_on)
+                and not self._controls_on and not self._masks_on and not self._logprobs_on)
 
     def _spec_config_for(self, T, max_new_tokens):
         """-> the speculative configuration the request of T prompt positions will run with, or None (plain steps)"""
@@ -1667,14 +1779,16 @@ class ChatTSForCausalLM:
         return Ts
 
     @torch.no_grad()
-    def generate_batch(self, requests, max_new_tokens=64, eos_token_id=None, sync_every=8, logprobs=None, controls=None):
+    def generate_batch(self, requests, max_new_tokens=64, eos_token_id=None, sync_every=8, logprobs=None, controls=None, masks=None):
         """Continuous batching over `max_batch` cache slots.  requests: list of (ids, series [n,2Lmax,1] | None,
         lengths | None).  A finished sequence frees its slot for the next waiting request at the next sync point.
         Returns the list of generated token lists, in request order.  logprobs: k for every request, or a list with one k / None per
         request -> (token lists, entry lists) (entries as in generate_one; None for a request that did not ask).
         controls: None = the slots keep their logit controls (set_sampling / set_slot_controls); a dict of repetition_penalty /
-        frequency_penalty / presence_penalty / min_p for every request, or a list with one dict / None (= the defaults) per request."""
+        frequency_penalty / presence_penalty / min_p for every request, or a list with one dict / None (= the defaults) per request.
+        masks: the same for logit_bias / allowed_token_ids / min_tokens (set_slot_masks; the ids min_tokens keeps away are eos_token_id)."""
         ctl = None if controls is None else self._request_controls(controls, len(requests))
+        msk = None if masks is None else self._request_masks(masks, len(requests), max_new_tokens)
         ks = list(logprobs) if isinstance(logprobs, (list, tuple)) else [logprobs] * len(requests)
         if len(ks) != len(requests):
             raise ValueError("logprobs: one value per request")
@@ -1685,7 +1799,8 @@ class ChatTSForCausalLM:
         if want:
             self.set_logprobs(True)
         if self.max_batch < 2:
-            outs = [self.generate_one(i, s, l, max_new_tokens, eos_token_id, logprobs=k, controls=None if ctl is None else (ctl[j] or {}))
+            outs = [self.generate_one(i, s, l, max_new_tokens, eos_token_id, logprobs=k, controls=None if ctl is None else (ctl[j] or {}),
+                                      masks=None if msk is None else (msk[j] or {}))
                     for j, ((i, s, l), k) in enumerate(zip(requests, ks))]
             if logprobs is None:
                 return outs
@@ -1733,6 +1848,8 @@ class ChatTSForCausalLM:
                         free.remove(s)
                         if ctl is not None:
                             self.set_slot_controls(s, **(ctl[r] or {}))
+                        if msk is not None:
+                            self.set_slot_masks(s, **(msk[r] or {}), end_ids=_eos_set(eos_token_id))
                         items.append((s, ids, series, lengths, max_new_tokens))
                         members.append((s, r))
                     try:
@@ -1754,6 +1871,8 @@ class ChatTSForCausalLM:
                 s = self.pick_slot(free, self._request_idents(ids, series, lengths))
                 if ctl is not None:
                     self.set_slot_controls(s, **(ctl[waiting[-1]] or {}))
+                if msk is not None:
+                    self.set_slot_masks(s, **(msk[waiting[-1]] or {}), end_ids=_eos_set(eos_token_id))
                 try:
                     self._admit(s, ids, series, lengths, max_new_tokens)
                 except RuntimeError as e:                    # (the reservation is _admit's first change: nothing to undo)
@@ -1798,13 +1917,17 @@ class ChatTSForCausalLM:
 
     @torch.no_grad()
     def generate_one(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, sync_every=16,
-                     return_logits=False, logprobs=None, controls=None):
+                     return_logits=False, logprobs=None, controls=None, masks=None):
         """ids: un-expanded prompt ids (host list); series: [n, 2*Lmax, 1] tensor of this prompt's series.
         logprobs=k (0 <= k <= max_logprobs): also return one (logprob, rank, top-k [(id, logprob)]) entry per returned token, last in
         the result tuple (toks[, logits0], entries).  controls: None = slot 0 keeps its logit controls; a dict of repetition_penalty /
-        frequency_penalty / presence_penalty / min_p (missing = default) sets them for this request."""
+        frequency_penalty / presence_penalty / min_p (missing = default) sets them for this request.  masks: the same for logit_bias /
+        allowed_token_ids / min_tokens (set_slot_masks; the ids min_tokens keeps away are eos_token_id)."""
         if controls is not None:
             self.set_slot_controls(0, **controls)
+        if masks is not None:
+            self.check_masks(**masks, max_tokens=max_new_tokens)
+            self.set_slot_masks(0, **masks, end_ids=_eos_set(eos_token_id))
         if logprobs is not None:
             self._check_logprobs(logprobs)
             self.set_logprobs(True)
@@ -1847,12 +1970,15 @@ class ChatTSForCausalLM:
             raise ValueError(f"logprobs={k!r} must be an integer in 0..max_logprobs={self.max_logprobs}")
 
     @torch.no_grad()
-    def generate_stream(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, chunk=1, controls=None):
+    def generate_stream(self, ids, series=None, lengths=None, max_new_tokens=64, eos_token_id=None, chunk=1, controls=None, masks=None):
         """Generator over the new tokens of ONE request: yields a list of token ids every `chunk` decode steps (chunk=1: token by
         token, what an SSE stream / HF TextStreamer consumes; each yield costs one device->host read of the tokens so far).
         Stops after an EOS token (which is yielded) or max_new_tokens.  Same kernels and tokens as generate_one (controls too)."""
         if controls is not None:
             self.set_slot_controls(0, **controls)
+        if masks is not None:
+            self.check_masks(**masks, max_tokens=max_new_tokens)
+            self.set_slot_masks(0, **masks, end_ids=_eos_set(eos_token_id))
         eos = _eos_set(eos_token_id)
         self._prefill_request(ids, series, lengths, max_new_tokens)
         produced, sent = 1, 0
@@ -1894,7 +2020,7 @@ class ChatTSForCausalLM:
     def generate(self, input_ids=None, attention_mask=None, timeseries=None, max_new_tokens=64, max_length=None,
                  streamer=None, eos_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None,
                  seed=0, synced_gpus=False, valid_lengths=None, repetition_penalty=None, min_p=None, prompt_lookup_num_tokens=None,
-                 max_matching_ngram_size=None, **kw):
+                 max_matching_ngram_size=None, min_new_tokens=None, **kw):
         """model.generate(**inputs, max_new_tokens=...) -> LongTensor [B, T_in + new] (README.md:102, demo_hf.ipynb
         cell 5).  Greedy unless do_sample=True, like HF; with do_sample the HF GenerationConfig defaults apply to what is
         not given (temperature 1.0, top_k 50, top_p 1.0; the reference's deepspeed driver passes temperature=0.2,
@@ -1902,10 +2028,15 @@ class ChatTSForCausalLM:
         right-padded with pad_token_id.  A flat `timeseries` tensor is consumed across the batch in prompt order.
         repetition_penalty and min_p have HF's meaning: the penalty applies with and without do_sample, min_p only with it.
         prompt_lookup_num_tokens=k (HF's name; max_matching_ngram_size=n, default 2 like HF): prompt-lookup speculative decoding for
-        THIS call, when it is greedy and has no repetition penalty; otherwise the two are ignored with a warning."""
+        THIS call, when it is greedy, has no repetition penalty and no min_new_tokens; otherwise the two are ignored with a warning.
+        min_new_tokens=k has HF's meaning (no EOS token among the first k new tokens): min_tokens of set_slot_masks."""
         self._spec_call = None
+        if min_new_tokens is not None and (isinstance(min_new_tokens, bool) or not isinstance(min_new_tokens, int) or min_new_tokens < 0):
+            raise ValueError(f"min_new_tokens must be an integer >= 0, got {min_new_tokens!r}")
+        if not min_new_tokens:
+            self.set_logit_masks(False)              # per call, like the sampling mode: a plain call runs the plain selection
         if prompt_lookup_num_tokens is not None:
-            greedy = not do_sample and (repetition_penalty is None or float(repetition_penalty) == 1.0)
+            greedy = not do_sample and (repetition_penalty is None or float(repetition_penalty) == 1.0) and not min_new_tokens
             call = parse_speculative_config({"method": "ngram", "num_speculative_tokens": prompt_lookup_num_tokens,
                                              "prompt_lookup_max": 2 if max_matching_ngram_size is None else max_matching_ngram_size,
                                              "prompt_lookup_min": 1}, self.plan.world, self.max_batch)
@@ -1914,15 +2045,15 @@ class ChatTSForCausalLM:
             else:
                 import warnings
                 warnings.warn("prompt_lookup_num_tokens is ignored: speculative decoding serves greedy requests without a repetition "
-                              "penalty only")
+                              "penalty and without min_new_tokens only")
         try:
             return self._generate(input_ids, attention_mask, timeseries, max_new_tokens, max_length, streamer, eos_token_id, do_sample,
-                                  temperature, top_k, top_p, seed, valid_lengths, repetition_penalty, min_p)
+                                  temperature, top_k, top_p, seed, valid_lengths, repetition_penalty, min_p, min_new_tokens)
         finally:
             self._spec_call = None
 
     def _generate(self, input_ids, attention_mask, timeseries, max_new_tokens, max_length, streamer, eos_token_id, do_sample,
-                  temperature, top_k, top_p, seed, valid_lengths, repetition_penalty, min_p):
+                  temperature, top_k, top_p, seed, valid_lengths, repetition_penalty, min_p, min_new_tokens=None):
         if do_sample:
             self.set_sampling(1.0 if temperature is None else temperature, 50 if top_k is None else top_k,
                               1.0 if top_p is None else top_p, seed, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
@@ -1947,18 +2078,19 @@ class ChatTSForCausalLM:
             cursor += n_ts
             reqs.append((seq, ser, lens))
         budget = max_new_tokens if max_length is None else max(1, max_length - max(len(r[0]) for r in reqs))
+        masks = {"min_tokens": min(int(min_new_tokens), budget)} if min_new_tokens else None
         if self.max_batch > 1 and len(reqs) > 1 and streamer is None and (self.plan.world == 1 or self._tp is not None):
-            outs = self.generate_batch(reqs, budget, eos_token_id)          # continuous batching over the cache slots
+            outs = self.generate_batch(reqs, budget, eos_token_id, masks=masks)          # continuous batching over the cache slots
         else:
             outs = []
             if streamer is not None:          # HF generate(): the prompt goes to the streamer first, then every token as it is made
                 streamer.put(ids)
             for seq, ser, lens in reqs:
                 if streamer is None:
-                    toks = self.generate_one(seq, ser, lens, budget, eos_token_id)
+                    toks = self.generate_one(seq, ser, lens, budget, eos_token_id, masks=masks)
                 else:
                     toks = []
-                    for new in self.generate_stream(seq, ser, lens, budget, eos_token_id, chunk=1):
+                    for new in self.generate_stream(seq, ser, lens, budget, eos_token_id, chunk=1, masks=masks):
                         for t in new:
                             streamer.put(torch.tensor([t]))
                         toks += new

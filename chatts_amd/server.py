@@ -74,7 +74,7 @@ def render_chat(messages, default_system=DEFAULT_SYSTEM):
     return prompt, series
 
 
-def sampling_from_body(body, default_max_tokens=512, max_num_seqs=None):
+def sampling_from_body(body, default_max_tokens=512, max_num_seqs=None, vocab_size=None):
     mt = body.get("max_completion_tokens") or body.get("max_tokens") or default_max_tokens
     temp = body.get("temperature")
     top_p = body.get("top_p")
@@ -103,10 +103,22 @@ def sampling_from_body(body, default_max_tokens=512, max_num_seqs=None):
             if not isinstance(body["include_stop_str_in_output"], bool):
                 raise ValueError("include_stop_str_in_output must be a boolean")
             out["include_stop_str_in_output"] = body["include_stop_str_in_output"]
+        # logit_bias (OpenAI: {"id": bias}, clamped to [-100, 100] as vLLM's OpenAI layer does), allowed_token_ids and min_tokens
+        # (vLLM's extra fields): the same rule
+        if body.get("logit_bias") is not None:
+            lb = body["logit_bias"]
+            if not isinstance(lb, dict):
+                raise ValueError(f"logit_bias must be an object of token id -> bias, got {lb!r}")
+            out["logit_bias"] = {k: (min(100.0, max(-100.0, float(v))) if isinstance(v, (int, float)) and not isinstance(v, bool)
+                                     and abs(v) != float("inf") and v == v else v) for k, v in lb.items()}
+        if body.get("allowed_token_ids") is not None:
+            out["allowed_token_ids"] = body["allowed_token_ids"]
+        if body.get("min_tokens") is not None:
+            out["min_tokens"] = body["min_tokens"]
     except (TypeError, ValueError) as e:
         raise ValueError(f"malformed sampling parameter: {e}")
     from .sampling import validate_n, validate_sampling
-    validate_sampling(**out)             # ValueError -> 400 (never reaches the engine thread)
+    validate_sampling(**out, vocab_size=vocab_size)             # ValueError -> 400 (never reaches the engine thread)
     if "n" in out:
         validate_n(out["n"], out.get("best_of"), max_num_seqs)
     return out
@@ -222,7 +234,8 @@ def create_app(engine_thread, tokenizer, served_model_name="chatts", limit_times
                     raise ValueError(f"prompt holds {prompt.count('<ts><ts/>')} <ts><ts/> placeholders but {len(series)} timeseries")
             if len(series) > limit_timeseries:
                 raise ValueError(f"At most {limit_timeseries} timeseries may be provided in one prompt, got {len(series)}")
-            sp = sampling_from_body(body, default_max_tokens, getattr(getattr(engine_thread, "engine", None), "nslots", None))
+            eng = getattr(engine_thread, "engine", None)
+            sp = sampling_from_body(body, default_max_tokens, getattr(eng, "nslots", None), getattr(eng, "vocab_size", None))
             lpk = logprobs_from_body(body, chat, max_logprobs)
             if lpk is not None:                  # (only then: an engine without logprobs never sees the keyword)
                 sp["logprobs"] = lpk

@@ -554,6 +554,43 @@ int chatts_logit_state_update(int32_t* state, int64_t state_stride, int batch, i
                               const int64_t* token, chatts_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Logit masks (logit_masks.hip): allowed_token_ids, logit_bias and min_tokens, with vLLM's names and meaning - the controls that
+ * constrain WHICH token may be chosen.  They come first in vLLM V1's order: raw logits -> allowed_token_ids -> logit_bias -> min_tokens
+ * -> repetition -> frequency and presence -> ... (the logit controls above), so with both on the penalties read args.out of this pass.
+ *   allowed_token_ids  rows with allow_on != 0: every id whose bit is clear becomes -inf.  Bit of GLOBAL id i: word i / 32, bit i % 32 of
+ *                      the row's allow_stride words (>= ceil((vocab_offset + vocab) / 32)).
+ *   logit_bias         l[id] += bias, one float32 add, for the row's first bias_n (<= bias_stride) pairs (bias_ids, bias_val); the ids
+ *                      of a row are DISTINCT (the caller guarantees it); -inf + b stays -inf.
+ *   min_tokens         while step_dev[row] < min_tokens[row] (the row's generated-token counter, 0 when its first token is chosen) the
+ *                      row's first end_n (<= end_stride) end_ids - the ids that would end the sequence - become -inf.
+ * Ids are global; those outside the slice [vocab_offset, vocab_offset + vocab) are skipped.  The raw logits are only read; the result
+ * goes to args.out (another buffer).  A row with nothing set is copied bit for bit, NaN payloads included.  Row b of every array belongs
+ * to row b of the logits; every per-row array is NULL-able (= that control is off for all rows: allow needs allow_bits and allow_on,
+ * the bias its three arrays, min_tokens its three arrays and step_dev).  Copy, -inf and one add: no atomics, no reductions, the same
+ * logits and settings give the same bits.  Two launches (the dense pass; the sparse pass, skipped when neither bias nor min_tokens
+ * arrays are given); graph-capturable, neither allocates nor synchronises.  vocab <= 2^31 - 1 - vocab_offset.
+ * ------------------------------------------------------------------------------------------- */
+#define CHATTS_LOGIT_BIAS_MAX 1024
+#define CHATTS_LOGIT_END_IDS_MAX 64
+typedef struct ChattsLogitMaskArgs {
+  float* out;                     /* [rows, out_stride] masked logits */
+  int64_t out_stride;             /* >= vocab */
+  const uint32_t* allow_bits;     /* [rows, allow_stride] */
+  int64_t allow_stride;           /* words per row */
+  const int32_t* allow_on;        /* [rows] 0 = the row has no allow list */
+  const int32_t* bias_ids;        /* [rows, bias_stride] */
+  const float* bias_val;          /* [rows, bias_stride] */
+  const int32_t* bias_n;          /* [rows] pairs in use */
+  int64_t bias_stride;            /* 1 .. CHATTS_LOGIT_BIAS_MAX */
+  const int32_t* end_ids;         /* [rows, end_stride] */
+  const int32_t* end_n;           /* [rows] ids in use */
+  const int32_t* min_tokens;      /* [rows] 0 = off */
+  int64_t end_stride;             /* 1 .. CHATTS_LOGIT_END_IDS_MAX */
+} ChattsLogitMaskArgs;
+int chatts_logit_masks_apply(const float* logits, int batch, int64_t logits_stride, int64_t vocab, int64_t vocab_offset,
+                             const ChattsLogitMaskArgs* args, const int32_t* step_dev, chatts_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fork (kv_fork.hip): n samples of one prompt from ONE prefill.  What the siblings need from the prompt - its K / V rows and, with
  * logit controls, the prompt marks of the state row - is copied from the slot that was prefilled to m other slots in one launch each:
  * every 16-byte unit of the source is read once and written m times, a wave access covers whole rows.  The first tokens are then m + 1
@@ -834,6 +871,22 @@ int chatts_decoder_select_tokens_controlled(ChattsDecoder*, const float* logits,
                                             float* token_logit, int64_t* out_tokens, int64_t out_stride, int32_t* step_dev,
                                             int32_t* pos_dev, int pos_limit, const ChattsSamplingArgs* override_or_null,
                                             const ChattsLogitControlArgs* controls_or_null, chatts_stream_t stream);
+
+/* Logit masks of every selection of this decoder (chatts_decoder_select_tokens and the decode steps, whose row b is cache slot b):
+ * NULL (default) = off, the selection is exactly what it is without the feature.  Otherwise (copied) every selection first runs
+ * chatts_logit_masks_apply with the rows' step counters, then the logit controls (when set) on args.out, and selects from the last
+ * buffer written; the selection's token_logit is the logit it read.  Under tensor parallelism the logits are first gathered into
+ * buffers.logits_full (chatts_allgather) and every rank runs the passes on the full vocabulary with offset 0 (out rows of vocab_local *
+ * tp_world cells): identical tokens on every rank.  Changing it invalidates any hipGraph captured over a decode step. */
+int chatts_decoder_set_logit_masks(ChattsDecoder*, const ChattsLogitMaskArgs* args_or_null);
+/* chatts_decoder_select_tokens with the logit controls AND the logit masks of THIS call (row b of both <-> row b of the logits: a
+ * request admitted into cache slot s passes the arrays advanced by s); NULL = the decoder's own setting of that one.  Masks with
+ * min_tokens arrays need step_dev. */
+int chatts_decoder_select_tokens_masked(ChattsDecoder*, const float* logits, int batch, int64_t logits_stride, int64_t* token,
+                                        float* token_logit, int64_t* out_tokens, int64_t out_stride, int32_t* step_dev,
+                                        int32_t* pos_dev, int pos_limit, const ChattsSamplingArgs* override_or_null,
+                                        const ChattsLogitControlArgs* controls_or_null, const ChattsLogitMaskArgs* masks_or_null,
+                                        chatts_stream_t stream);
 
 /* Token selection of chatts_decoder_decode_step(_batched): NULL (default) = greedy argmax; otherwise the sampler above
  * with these parameters (copied).  Changing it invalidates any hipGraph captured over a decode step. */
